@@ -27,8 +27,13 @@ synthetic batch" (DP=N over RCCL for N>1).
   steps as ``warmup_extra_steps``;
 * K steps timed between barrier + synchronize on both sides, MAX over ranks; hipEvents around
   each graph replay give the median step and the slowest rank's median;
-* after timing, validation metrics on a held-out positional 30% split
-  (outside the timed region).
+* a plain run stops there: set up, warm up, time the K steps, print the JSON line;
+* ``--dump-outputs DIR``: what the last timed step returned (the loss, the updated parameters and
+  Adam moments) as ``DIR/<name>.npy``.  The training state is then put back to the seeded initial
+  state right before the timed window, so the arrays depend on the arguments alone (the clock
+  warmup runs a wall-time-dependent number of steps);
+* ``--full``: after timing, validation metrics on a held-out positional 30% split and the iid-data
+  control (outside the timed region).
 """
 from __future__ import annotations
 
@@ -128,7 +133,14 @@ def _parse():
                     help="after the W warmup steps, keep replaying untimed warmup steps until this much wall "
                          "time has passed (the chip ramps its clock over the first ~100 ms of load; a training "
                          "run spends its life at the steady clock).  0 = exactly W warmup steps")
-    ap.add_argument("--no-eval", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the validation metrics on the held-out "
+                         "split and the iid-data control (JSON fields val / val_iid)")
+    ap.add_argument("--no-eval", action="store_true", help="with --full: skip the validation metrics")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (loss, parameters, Adam moments) "
+                         "as DIR/<name>.npy (float32; at most 64 MB in all, a fixed seeded sample of a larger array); "
+                         "the timed steps then start from the seeded initial state")
     ap.add_argument("--impl", default="fused", choices=["fused", "gemm", "torch"],
                     help="fused = our HIP kernels (headline: the fused train kernel for --model mlp, the GEMM engine "
                          "for mlp-wide); gemm = the per-layer GEMM engine for --model mlp too; torch = plain "
@@ -212,6 +224,71 @@ def _params_identical(model, world: int):
     got = [torch.empty_like(flat) for _ in range(world)]
     dist.all_gather(got, flat)
     return all(torch.equal(got[0], g) for g in got[1:])
+
+
+class _InitialState:
+    """--dump-outputs: a copy of a model's training state (parameters, Adam moments and step counter, the
+    packed weight images the kernels read) taken before the first step; ``restore()`` copies it back in
+    place, so captured hipGraphs keep their pointers."""
+
+    def __init__(self, model):
+        import copy
+
+        self.model = model
+        if isinstance(model, _TorchBaseline):
+            self.net = copy.deepcopy(model.net.state_dict())
+            self.opt = copy.deepcopy(model.opt.state_dict())
+        else:
+            self.live = [t for t in (getattr(model, n, None) for n in ("params", "m", "v", "state", "img", "shadow"))
+                         if isinstance(t, torch.Tensor)]
+            self.saved = [t.clone() for t in self.live]
+
+    def restore(self):
+        import copy
+
+        if isinstance(self.model, _TorchBaseline):
+            self.model.net.load_state_dict(self.net)
+            self.model.opt.load_state_dict(copy.deepcopy(self.opt))
+        else:
+            for t, s in zip(self.live, self.saved):
+                t.copy_(s)
+        torch.cuda.synchronize()
+
+
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: budget for all arrays together
+
+
+def _step_outputs(model, loss_t) -> dict:
+    """What a caller of the timed step holds after it: the returned loss and the updated optimizer state."""
+    out = {"loss": loss_t.detach().reshape(-1)}
+    if isinstance(model, _TorchBaseline):
+        ps = list(model.net.parameters())
+        out["params"] = torch.cat([p.detach().reshape(-1) for p in ps])
+        for name, key in (("adam_m", "exp_avg"), ("adam_v", "exp_avg_sq")):
+            out[name] = torch.cat([model.opt.state[p][key].reshape(-1) for p in ps])
+    else:
+        out.update({"params": model.params, "adam_m": model.m, "adam_v": model.v})
+    return out
+
+
+def _dump_outputs(path: str, arrays: dict) -> dict:
+    """Write each array as ``path/<name>.npy`` (float32).  An array over its share of DUMP_BYTES is
+    reduced to a fixed seeded sample of its elements (ascending positions, the same in every run)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // 4 // len(arrays)
+    info = {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > cap:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, n, (cap,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+        info[name] = {"elements": n, "written": t.numel()}
+    return info
 
 
 def main():
@@ -329,7 +406,8 @@ def main():
         def step(i):
             return model.step(boff(i))
 
-    use_graph = bool(a.graph) and not getattr(model, "no_graph", False) and (
+    init_state = _InitialState(model) if a.dump_outputs else None
+    use_graph =bool(a.graph) and not getattr(model, "no_graph", False) and (
         world == 1 or getattr(model, "graph_safe", False))
     loss_t = None
     tw = time.perf_counter()
@@ -356,6 +434,7 @@ def main():
             model = FusedSmallMLP(dev, loss=a.loss, lr=a.lr, seed=a.seed, process_group=group, comm="rccl",
                                   dtype=a.dtype)
             model.broadcast_parameters()
+            init_state = _InitialState(model) if a.dump_outputs else None
             comm_fallback = "xgmi step error -> rccl"
             use_graph = bool(a.graph) and not getattr(model, "no_graph", False) and getattr(model, "graph_safe", False)
             for i in range(a.warmup if not use_graph else min(a.warmup, 1)):
@@ -423,6 +502,8 @@ def main():
         clock_warmup(lambda: step(next(wi)), 1)
         runs = [(lambda i=i: step(i), 1) for i in range(a.steps)]
 
+    if init_state is not None:
+        init_state.restore()  # the timed steps start from the seeded state, however many warmup steps ran
     ev0 = [torch.cuda.Event(enable_timing=True) for _ in runs]
     ev1 = [torch.cuda.Event(enable_timing=True) for _ in runs]
     if world > 1:
@@ -455,8 +536,12 @@ def main():
               "stable number", file=sys.stderr)
     loss = float(loss_t.reshape(-1)[0].item()) if loss_t is not None else float("nan")
 
+    dumped = None
+    if a.dump_outputs and rank == 0 and loss_t is not None:
+        dumped = _dump_outputs(a.dump_outputs, _step_outputs(model, loss_t))
+
     ev, ev_iid = {}, {}
-    if not a.no_eval:
+    if a.full and not a.no_eval:
         del draws
         torch.cuda.empty_cache()
         va, vb = sh.val
@@ -520,6 +605,7 @@ def main():
                         "steps_spread": spread, "resident_train_gb": resident_gb,
                         "logical_sequence_gb_per_gpu": n_loc * 8 / 2**30},
             **extra,
+            **({"dumped_outputs": dumped} if dumped is not None else {}),
         }
         print(json.dumps(out), flush=True)
     if hasattr(model, "close"):

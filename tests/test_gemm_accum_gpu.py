@@ -84,7 +84,7 @@ def test_bench_two_ranks_share_one_task():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = ["--gpus", "2", "--dist-backend", "gloo", "--steps", "40", "--warmup", "2", "--batch", "65536",
-            "--draws-per-gpu", str(1 << 21)]
+            "--draws-per-gpu", str(1 << 21), "--full"]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args], capture_output=True, text=True,
                        timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]

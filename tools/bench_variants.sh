@@ -14,7 +14,7 @@ while IFS= read -r a; do
 done <<'LIST'
 --impl torch --steps 5 --warmup 2 --no-eval
 --impl gemm --steps 10 --warmup 2 --no-eval
---loss bce --steps 20 --warmup 5
+--loss bce --steps 20 --warmup 5 --full
 --model mlp-wide --comm-dtype bf16 --steps 5 --warmup 2 --no-eval
 --graph 0 --steps 20 --warmup 5 --no-eval
 --batch 262144 --steps 20 --warmup 5 --no-eval

@@ -21,12 +21,12 @@ run gbdt_trace 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/
 run fused_pmc 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $OUT/fused_pmc -o run -- python3 bench.py --steps 6 --warmup 2 --graph 0 --no-eval
 run fused_pmc2 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/fused_pmc2 -o run -- python3 bench.py --steps 6 --warmup 2 --graph 0 --no-eval
 run wide_pmc 400 rocprofv3 --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE FETCH_SIZE --output-format csv -d $OUT/wide_pmc -o run -- python3 bench.py --model mlp-wide --steps 3 --warmup 1 --graph 0 --no-eval
-run bench_headline 300 python3 bench.py --steps 100 --warmup 10
+run bench_headline 300 python3 bench.py --steps 100 --warmup 10 --full
 run bench_torch 300 python3 bench.py --steps 20 --warmup 3 --graph 0 --impl torch --no-eval
-run bench_wide 300 python3 bench.py --model mlp-wide --steps 10 --warmup 3
-run bench_mega_data 300 python3 bench.py --device-data-gb 200 --steps 50 --warmup 5
-run bench_mega_batch 300 python3 bench.py --device-data-gb 200 --batch 268435456 --steps 10 --warmup 2
-run bench_wide_mega 400 python3 bench.py --model mlp-wide --device-data-gb 100 --accum 16 --steps 4 --warmup 1
+run bench_wide 300 python3 bench.py --model mlp-wide --steps 10 --warmup 3 --full
+run bench_mega_data 300 python3 bench.py --device-data-gb 200 --steps 50 --warmup 5 --full
+run bench_mega_batch 300 python3 bench.py --device-data-gb 200 --batch 268435456 --steps 10 --warmup 2 --full
+run bench_wide_mega 400 python3 bench.py --model mlp-wide --device-data-gb 100 --accum 16 --steps 4 --warmup 1 --full
 run gemm_bench 300 python3 tools/gemm_bench.py
 run rf_bench 300 python3 tools/rf_bench.py
 run gbdt_bench 300 python3 tools/gbdt_bench.py

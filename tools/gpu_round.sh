@@ -36,8 +36,8 @@ for stage in "$@"; do
     tail -1 $O/pytest.log
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 4; }
     tail -1 $O/smoke.log
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { tail $O/bench_driver.err; exit 5; }
-    timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 6; }
+    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err || { tail $O/bench_driver.err; exit 5; }
+    timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 6; }
     summ $O/bench_driver.json driver && summ $O/bench_default.json default || exit 7
     ;;
   headline-prof)
@@ -80,12 +80,12 @@ for stage in "$@"; do
     cat $O/gbdt_bench.jsonl
     ;;
   fp32)
-    timeout -k 10 300 python bench.py --dtype fp32 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 16; }
+    timeout -k 10 300 python bench.py --dtype fp32 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 16; }
     summ $O/bench.json fp32 || exit 17
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python bench.py --dtype fp32 --steps 20 --warmup 5 --no-eval > $O/trace.log 2>&1 || { tail $O/trace.log; exit 18; }
     ;;
   wide)
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python bench.py --model mlp-wide --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 19; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python bench.py --model mlp-wide --steps 10 --warmup 3 --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 19; }
     summ $O/bench.json wide || exit 20
     timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/overlap -o run -- python tools/wide_overlap.py > $O/overlap.jsonl 2> $O/overlap.err || { tail $O/overlap.err; exit 21; }
     python tools/wide_overlap.py report $O/overlap/run_kernel_trace.csv > $O/overlap_report.jsonl && cat $O/overlap.jsonl
@@ -120,7 +120,7 @@ for stage in "$@"; do
     ;;
   hbm-fill)
     for pl in 0.9 0.7; do
-      timeout -k 10 300 python bench.py --device-data-gb -1 --batch 268435456 --steps 10 --warmup 2 --planted $pl > $O/fill_$pl.json 2> $O/fill_$pl.err || { tail $O/fill_$pl.err; exit 29; }
+      timeout -k 10 300 python bench.py --device-data-gb -1 --batch 268435456 --steps 10 --warmup 2 --planted $pl --full > $O/fill_$pl.json 2> $O/fill_$pl.err || { tail $O/fill_$pl.err; exit 29; }
       summ $O/fill_$pl.json fill_$pl || exit 30
     done
     ;;
@@ -138,9 +138,9 @@ for stage in "$@"; do
   dp2)
     # 2-rank bench.py rehearsal of the DP path with both ranks on the one GPU (gloo control plane; the fused
     # xGMI exchange carries the gradients), then the 1-rank driver shape
-    timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --dist-backend gloo > $O/bench_dp2.json 2> $O/bench_dp2.err || { grep -v amdgpu.ids $O/bench_dp2.err | tail -20; exit 43; }
+    timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --dist-backend gloo --full > $O/bench_dp2.json 2> $O/bench_dp2.err || { grep -v amdgpu.ids $O/bench_dp2.err | tail -20; exit 43; }
     grep '^{' $O/bench_dp2.json | cut -c1-600
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_dp1.json 2> $O/bench_dp1.err || { tail $O/bench_dp1.err; exit 44; }
+    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_dp1.json 2> $O/bench_dp1.err || { tail $O/bench_dp1.err; exit 44; }
     summ $O/bench_dp1.json dp1 || exit 45
     ;;
   gbdt-host)
