@@ -89,33 +89,68 @@ EM_DEVICE void v6_softmax_split(const char* smem, const f32x16 (&z2)[2], uint64_
   if (PERM) tmask = phys_targets(tmask);
   constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
   const f32x2 L2E2 = {L2E, L2E};
+  const uint32_t tlo = (uint32_t)tmask, thi = (uint32_t)(tmask >> 32);
+  const int nm = __builtin_popcount(tlo) + __builtin_popcount(thi & 0x3FFFFu);  // bits 0..49
+  const int ns = __builtin_popcount(thi & (PERM ? 0xFFFC0000u : 0x3FFC0000u));   // bits 50..61 (PERM: 50..63)
+  // SD (table at 256, the K7 windowed layout): the COUNT-SCALED target table.  Row R = 1..14 (256 B each,
+  // at 256 R) holds, for a class with R - 1 targets, entry nibble -> 4 floats y * (-1 / n): the very product
+  // dZ2 = p - y / n adds (0 * ni = -0.0 and the n = 0 row included), so the tile spends no multiply, rcp or
+  // select on the targets and the target dot accumulates (-y / n) z directly.  A lookup is ONE VALU: byte g
+  // of the pattern = nibble | row << 4, shifted left by 4 through an SDWA byte select.  Row 15 holds -y
+  // ({-1, -0}): lanes whose class has more than 13 targets (no draw has; the kernel accepts any mask) read
+  // it, and a wave-uniform cold block multiplies that tile's targets by 1 / n (other lanes: by 1), which
+  // gives the same bits.  Tile 1's nibble of registers 8-11 (main | star) is looked up in both rows.
+  constexpr bool SD = YL == 256 && PERM;
+  uint32_t rowm = 0, rows = 0;
+  bool cold = false;
+  if constexpr (SD) {
+    // row << 4 in every byte: v_perm_b32 with selector 0 replicates byte 0 (a full-rate VALU; a multiply by
+    // 0x10101010 is a quarter-rate v_mul_lo_u32)
+    const uint32_t rm = (uint32_t)(__builtin_elementwise_min(nm, 14) << 4) + 16u;
+    const uint32_t rs = (uint32_t)(__builtin_elementwise_min(ns, 14) << 4) + 16u;
+    rowm = __builtin_amdgcn_perm(rm, rm, 0u);
+    rows = __builtin_amdgcn_perm(rs, rs, 0u);
+    cold = __builtin_amdgcn_ballot_w64(__builtin_elementwise_max(nm, ns) > 13) != 0;
+  }
   auto targets = [&](int u, float (&yb)[16]) {
     const uint32_t tmh = (uint32_t)(tmask >> (32 * u)) >> (4 * h);
-    // SDWA form (table at 256, the K7 windowed layout): byte g of sp = nibble 8g + 16, so one byte-select
-    // shift per lookup gives 256 + 16 nib -- 5 VALU per word instead of 8
-    constexpr bool SD = YL == 256 && PERM;
-    const uint32_t sp = (tmh & 0x0F0F0F0Fu) | 0x10101010u;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      uint32_t off;
-      if constexpr (SD) {
-        off = g == 0 ? sdwa_byte_shl<0, 4>(sp) : g == 1 ? sdwa_byte_shl<1, 4>(sp) : g == 2 ? sdwa_byte_shl<2, 4>(sp)
-                                                                                          : sdwa_byte_shl<3, 4>(sp);
-      } else {
-        off = lut_off<YL, 4>(tmh, 8 * g);
+    if constexpr (SD) {
+      const uint32_t nb = tmh & 0x0F0F0F0Fu;
+      const uint32_t pm = nb | rowm, ps = nb | rows;  // tile 0: all main; tile 1: registers 0-9 main, 10-15 star
+      const f32x4 y0 = *reinterpret_cast<const f32x4*>(smem + sdwa_byte_shl<0, 4>(pm));
+      const f32x4 y1 = *reinterpret_cast<const f32x4*>(smem + sdwa_byte_shl<1, 4>(pm));
+      const f32x4 y3 = *reinterpret_cast<const f32x4*>(smem + sdwa_byte_shl<3, 4>(u == 0 ? pm : ps));
+      yb[0] = y0[0]; yb[1] = y0[1]; yb[2] = y0[2]; yb[3] = y0[3];
+      yb[4] = y1[0]; yb[5] = y1[1]; yb[6] = y1[2]; yb[7] = y1[3];
+      yb[12] = y3[0]; yb[13] = y3[1]; yb[14] = y3[2]; yb[15] = y3[3];
+      if (u == 0) {
+        const f32x4 y2 = *reinterpret_cast<const f32x4*>(smem + sdwa_byte_shl<2, 4>(pm));
+        yb[8] = y2[0]; yb[9] = y2[1]; yb[10] = y2[2]; yb[11] = y2[3];
+      } else {  // registers 8, 9 main | 10, 11 star: the entry's halves from the two rows
+        const f32x2 ym = *reinterpret_cast<const f32x2*>(smem + sdwa_byte_shl<2, 4>(pm));
+        const f32x2 ys = *reinterpret_cast<const f32x2*>(smem + sdwa_byte_shl<2, 4>(ps) + 8);
+        yb[8] = ym[0]; yb[9] = ym[1]; yb[10] = ys[0]; yb[11] = ys[1];
       }
-      const f32x4 y4 = *reinterpret_cast<const f32x4*>(smem + off);
-      yb[4 * g + 0] = y4[0]; yb[4 * g + 1] = y4[1]; yb[4 * g + 2] = y4[2]; yb[4 * g + 3] = y4[3];
+      if (__builtin_expect(cold, 0)) {
+        const float km = nm > 13 ? __builtin_amdgcn_rcpf((float)nm) : 1.f;
+        const float ks = ns > 13 ? __builtin_amdgcn_rcpf((float)ns) : 1.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) yb[i] *= out_cls<PERM>(u, i, 0) == 0 ? km : ks;
+      }
+    } else {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 y4 = *reinterpret_cast<const f32x4*>(smem + lut_off<YL, 4>(tmh, 8 * g));
+        yb[4 * g + 0] = y4[0]; yb[4 * g + 1] = y4[1]; yb[4 * g + 2] = y4[2]; yb[4 * g + 3] = y4[3];
+      }
     }
   };
   auto zpair = [&](int u, int i) { return f32x2{z2[u][i], z2[u][i + 1]}; };
   auto exp2 = [](f32x2 t) { return f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)}; };
   const bool h0 = h == 0;
-  const uint32_t tlo = (uint32_t)tmask, thi = (uint32_t)(tmask >> 32);
-  const int nm = __builtin_popcount(tlo) + __builtin_popcount(thi & 0x3FFFFu);  // bits 0..49
-  const int ns = __builtin_popcount(thi & (PERM ? 0xFFFC0000u : 0x3FFC0000u));   // bits 50..61 (PERM: 50..63)
-  const float inv_m = nm ? __builtin_amdgcn_rcpf((float)nm) : 0.f;
-  const float inv_s = ns ? __builtin_amdgcn_rcpf((float)ns) : 0.f;
+  // (SD: the table rows carry -1 / n)
+  const float inv_m = SD ? 0.f : nm ? __builtin_amdgcn_rcpf((float)nm) : 0.f;
+  const float inv_s = SD ? 0.f : ns ? __builtin_amdgcn_rcpf((float)ns) : 0.f;
   // target dots: tm[q] holds elements with (i & 3) >> 1 == q (x: even i, y: odd i), ts by i & 1
   f32x2 tm[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, ts = {0.f, 0.f};
   // ---- tile 0: outputs 0..31, all main.  step(j), j = 0..7, is issued between tile 1's F2 MFMAs by
@@ -233,6 +268,7 @@ EM_DEVICE void v6_softmax_split(const char* smem, const f32x16 (&z2)[2], uint64_
   const float rS = nm ? __builtin_amdgcn_rcpf(S) : 0.f;
   const float f0 = a0 * rS, f1 = a1 * rS, f_s = ns ? __builtin_amdgcn_rcpf(s_s) : 0.f;
   const float ni_m = -inv_m, ni_s = -inv_s;
+  auto yn = [](float y, float ni) { return SD ? y : y * ni; };  // SD: the table holds y * ni
   // (written per element: the compiler pairs these into v_pk_mul_f32 + v_pk_fma_f32 by itself, and the
   // explicit f32x2 form compiled to 8 more VALU)
 #pragma unroll
@@ -243,8 +279,8 @@ EM_DEVICE void v6_softmax_split(const char* smem, const f32x16 (&z2)[2], uint64_
       const int c0 = out_cls<PERM>(u, i, 0), c1 = out_cls<PERM>(u, i, 1);
       const float fm = u == 0 ? f0 : f1;
       if (c0 == c1) {
-        if (c0 == 0) dz[u][i] = __builtin_fmaf(dz[u][i], fm, yb[i] * ni_m);
-        if (c0 == 1) dz[u][i] = __builtin_fmaf(dz[u][i], f_s, yb[i] * ni_s);
+        if (c0 == 0) dz[u][i] = __builtin_fmaf(dz[u][i], fm, yn(yb[i], ni_m));
+        if (c0 == 1) dz[u][i] = __builtin_fmaf(dz[u][i], f_s, yn(yb[i], ni_s));
         if (c0 == 2) dz[u][i] = 0.f;
       } else if (c0 == 0) {
         dz[u][i] = __builtin_fmaf(dz[u][i], h0 ? fm : f_s, yb[i] * (h0 ? ni_m : ni_s));
@@ -253,7 +289,9 @@ EM_DEVICE void v6_softmax_split(const char* smem, const f32x16 (&z2)[2], uint64_
       }
     }
   }
-  float l = -(((tm[0].x + tm[0].y) + (tm[1].x + tm[1].y)) * inv_m + (ts.x + ts.y) * inv_s);
+  // SD: the target dots already carry -1 / n (the one result change: the loss moves in its last bits)
+  float l = SD ? ((tm[0].x + tm[0].y) + (tm[1].x + tm[1].y)) + (ts.x + ts.y)
+               : -(((tm[0].x + tm[0].y) + (tm[1].x + tm[1].y)) * inv_m + (ts.x + ts.y) * inv_s);
   if (h == 0)
     l += (nm ? M + __builtin_amdgcn_logf(S) * LN2 : 0.f) + (ns ? mx_s + __builtin_amdgcn_logf(s_s) * LN2 : 0.f);
   loss_acc += l;

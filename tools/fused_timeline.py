@@ -47,8 +47,7 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         per = e0.elapsed_time(e1) * 1e3 / 10
-        v8 = os.environ.get("EUROM_FUSED_V") in ("8", "9")  # v8 / v9: 12 waves, wall-clock marks in wave 0's spare lanes 10-14
-        T0 = FM.P_TOTAL + (10 if v8 else 128)
+        T0 = FM.P_TOTAL + 128
         raw = m.slabs[:nslab, T0:T0 + 4].contiguous().view(torch.int32).cpu().numpy()
         t = raw.astype(np.int64) & 0xFFFFFFFF
         t -= t[:, 0].min()
@@ -73,14 +72,11 @@ def main():
             print(f"   launch {rep}: loop median per XCC_ID:",
                   " ".join("%d:%.1f" % (k, np.median(lp[xc == k])) for k in range(8) if (xc == k).any()),
                   "| blockIdx%8 -> XCC_ID:", " ".join(str(int(np.bincount(xc[xcd == k]).argmax())) for k in range(8)))
-        nw = 12 if v8 else 8
+        nw = 8
         st = m.slabs[:nslab, FM.P_TOTAL:FM.P_TOTAL + 16 * nw].reshape(nslab, nw, 16)[:, :, :10].double().cpu().numpy()
         shared = os.environ.get("TL_SHARED", "1") == "1"  # FUSED_SHARED layout: waves 0-3 forward
-        if v8:
-            roles = (("forward", list(range(8))), ("backward", [8, 9, 10, 11]))
-        else:
-            roles = (("forward", [0, 1, 2, 3]), ("backward", [4, 5, 6, 7])) if shared else \
-                (("forward", [0, 1, 6, 7]), ("backward", [2, 3, 4, 5]))
+        roles = (("forward", [0, 1, 2, 3]), ("backward", [4, 5, 6, 7])) if shared else \
+            (("forward", [0, 1, 6, 7]), ("backward", [2, 3, 4, 5]))
         for nm, ws in roles:  # wave -> role map of the kernel
             v = st[:, ws, :].reshape(-1, 10).mean(0)
             tot = v.sum()

@@ -13,13 +13,11 @@
 #                                           forest.hip: SRC=... build_variant.sh rf_head), kernel stats
 #   bash tools/gpu_round.sh dp-proxy        one-GPU DP=8 small-MLP exchange proxy (tools/xgmi_budget.py)
 #   bash tools/gpu_round.sh hbm-fill        HBM-filling 256M-sample runs on p = 0.9 and p = 0.7
-#   bash tools/gpu_round.sh v8              K7 v8 (EUROM_FUSED_V=8): fused GPU tests, v6/v8 A/B, phase timeline
 #   bash tools/gpu_round.sh pmc-ab          two PMC passes of the train kernel per arm of PMC_ARMS
 #   bash tools/gpu_round.sh tests           pytest -m gpu over TESTS (default: the whole suite)
 #   bash tools/gpu_round.sh ab              tools/gpu_ab.sh with ARMS / ROUNDS / BENCH_ARGS
 #   bash tools/gpu_round.sh dp2             2-rank shared-GPU bench rehearsal + the 1-rank driver shape
 #   bash tools/gpu_round.sh gbdt-host       host-side profile of the GBDT reference fit
-#   bash tools/gpu_round.sh k7-trace        per-tile event trace of the v8 train kernel
 # (round 6 folded the one-off tools/gpu_gNN.sh batch scripts of rounds 3-5 into these stages; git history
 # keeps them)
 # Several stages run in order: bash tools/gpu_round.sh gbdt fp32
@@ -49,19 +47,9 @@ for stage in "$@"; do
       cat $O/timeline.txt
     fi
     ;;
-  v8)
-    # K7 v8 (three waves per SIMD): fused-kernel GPU tests on v8, same-box v6/v8 A/B, v8 phase timeline
-    EUROM_FUSED_V=8 timeout -k 10 400 python -u -m pytest tests/test_fused_mlp_gpu.py -x -v --timeout 120 --timeout-method thread > $O/pytest_v8.log 2>&1 || { tail -40 $O/pytest_v8.log; exit 30; }
-    tail -3 $O/pytest_v8.log
-    ARMS=${V8_ARMS:-"v6|EUROM_FUSED_V=6;v8|EUROM_FUSED_V=8"} ROUNDS=${V8_ROUNDS:-3} bash tools/gpu_ab.sh || exit 31
-    if [ -f euromillioner_amd/lib/ab/stamps.so ]; then
-      EUROM_FUSED_V=8 EUROM_NATIVE_LIB=$PWD/euromillioner_amd/lib/ab/stamps.so TL_B=1048576 timeout -k 10 200 python tools/fused_timeline.py > $O/timeline_v8.txt 2>&1 || { tail -20 $O/timeline_v8.txt; exit 32; }
-      cat $O/timeline_v8.txt
-    fi
-    ;;
   pmc-ab)
     # the same two PMC passes for each arm of PMC_ARMS="name|ENV=..;name2|ENV=.." (train-kernel counters, eager launches)
-    IFS=';' read -ra LIST <<< "${PMC_ARMS:-v6|EUROM_FUSED_V=6;v8|EUROM_FUSED_V=8}"
+    IFS=';' read -ra LIST <<< "${PMC_ARMS:-head|EUROM_X=0}"
     for arm in "${LIST[@]}"; do
       name=${arm%%|*}; envs=${arm#*|}
       for pass in 1 2; do
@@ -147,11 +135,6 @@ for stage in "$@"; do
     # host-side profile of the GBDT reference fit (tools/gbdt_fit_profile.py)
     timeout -k 10 300 python tools/gbdt_fit_profile.py > $O/gbdt_fit_profile.txt 2>&1 || { tail -20 $O/gbdt_fit_profile.txt; exit 46; }
     head -60 $O/gbdt_fit_profile.txt
-    ;;
-  k7-trace)
-    # per-tile event trace of the v8 train kernel (needs lib/ab/trace.so: build_variant.sh trace -DFUSED_TRACE=1)
-    EUROM_FUSED_V=8 EUROM_NATIVE_LIB=$PWD/euromillioner_amd/lib/ab/trace.so timeout -k 10 120 python tools/fused_trace.py > $O/trace.txt 2>&1 || { tail $O/trace.txt; exit 47; }
-    tail -9 $O/trace.txt
     ;;
   *) echo "unknown stage $stage"; exit 2;;
   esac
