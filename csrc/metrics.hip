@@ -44,9 +44,13 @@ EM_DEVICE uint64_t topk_mask(const float* z, int lo, int hi) {
   for (int o = lo; o < hi; ++o) {
     float v = z[o];
     int id = o;
+    // insertion (stable: earlier index wins ties).  Once v has taken slot k the displaced entries shift down
+    // unconditionally: the list is sorted, and a displaced entry that EQUALS the one below it is the earlier
+    // index of the two, so a strict compare there would drop it and keep the later one.
+    bool sw = false;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {  // insertion (stable: earlier index wins ties)
-      const bool sw = v > bv[k];
+    for (int k = 0; k < K; ++k) {
+      sw = sw || v > bv[k];
       const float tv = bv[k];
       const int ti = bi[k];
       bv[k] = sw ? v : tv;
