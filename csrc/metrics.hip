@@ -14,11 +14,9 @@
 // Samples are read as 64-bit feature masks (see em_rows_to_masks).
 // Partial sums per 256-sample block -> [nblocks][8] (summed on the host side in fp64).
 #include "common.h"
+#include "draw_topk.h"  // MAIN_BITS, STAR_BITS, topk_mask (shared with csrc/tickets.hip)
 
 namespace {
-
-constexpr uint64_t MAIN_BITS = (1ull << 50) - 1;
-constexpr uint64_t STAR_BITS = ((1ull << 12) - 1) << 50;
 
 EM_DEVICE uint64_t draw_mask8(const uint8_t* row) {
   uint64_t m = 0;
@@ -32,36 +30,6 @@ EM_DEVICE uint64_t draw_mask8(const uint8_t* row) {
     const uint32_t s = row[k];
     m |= (s >= 1 && s <= 12) ? (1ull << (49 + s)) : 0ull;
   }
-  return m;
-}
-
-template <int K>
-EM_DEVICE uint64_t topk_mask(const float* z, int lo, int hi) {
-  float bv[K];
-  int bi[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) { bv[k] = -3.0e38f; bi[k] = lo; }
-  for (int o = lo; o < hi; ++o) {
-    float v = z[o];
-    int id = o;
-    // insertion (stable: earlier index wins ties).  Once v has taken slot k the displaced entries shift down
-    // unconditionally: the list is sorted, and a displaced entry that EQUALS the one below it is the earlier
-    // index of the two, so a strict compare there would drop it and keep the later one.
-    bool sw = false;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      sw = sw || v > bv[k];
-      const float tv = bv[k];
-      const int ti = bi[k];
-      bv[k] = sw ? v : tv;
-      bi[k] = sw ? id : ti;
-      v = sw ? tv : v;
-      id = sw ? ti : id;
-    }
-  }
-  uint64_t m = 0;
-#pragma unroll
-  for (int k = 0; k < K; ++k) m |= 1ull << bi[k];
   return m;
 }
 

@@ -7,7 +7,8 @@ runs the whole pipeline (``Main.java:35``).  Here:
     euromillioner run [flags]          # same, with flags (reference defaults)
     euromillioner train --model mlp    # 62->128->62 MLP on the fused HIP path (DP via torchrun)
     euromillioner train --model mlp-wide | rf | gbdt
-    euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv]
+    euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv] [--tickets 5 --temperature 1.0]
+    euromillioner backtest --ckpt model.zip --tickets 16   # prize tiers of sampled tickets on the validation split
     euromillioner gen --n 1000000 --planted 0.9 --out draws.csv
     euromillioner info                 # device, native libraries, kernel inventory
 
@@ -48,6 +49,7 @@ _FLAGS = {
     "--check-sync-every": "dist.check_sync_every", "--avg-frequency": "dist.avg_frequency",
     "--max-restarts": "dist.max_restarts",
     "--profile-dir": "log.profile_dir", "--profile-steps": "log.profile_steps",
+    "--tickets": "tickets.n", "--temperature": "tickets.temperature", "--ticket-seed": "tickets.seed",
     "--ckpt": "ckpt.path", "--resume": "ckpt.resume", "--ckpt-every": "ckpt.every",
     "--log-level": "log.level", "--device": "device",
 }
@@ -85,6 +87,9 @@ def build_parser() -> argparse.ArgumentParser:
     p = sub.add_parser("predict", help="predict the next draw from a checkpoint")
     _add_common(p)
     p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "rf", "gbdt"])
+    p = sub.add_parser("backtest", help="play sampled tickets on every validation draw and count prize tiers")
+    _add_common(p)
+    p.add_argument("--model", default=None, choices=["mlp", "mlp-wide"])
     p = sub.add_parser("gen", help="write synthetic draws to CSV")
     p.add_argument("--n", "--n-draws", dest="n", type=int, default=None, help="draws to generate (same name as train --n-draws)")
     p.add_argument("--seed", type=int, default=0)
@@ -147,6 +152,10 @@ def main(argv=None) -> int:
             from .train import predict_next
 
             res = predict_next(cfg)
+        elif a.cmd == "backtest":
+            from .train import backtest
+
+            res = backtest(cfg)
         else:
             ap.print_help()
             return 2

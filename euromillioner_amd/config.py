@@ -137,6 +137,13 @@ class LogConfig:
 
 
 @dataclasses.dataclass
+class TicketConfig:
+    n: int = 0  # tickets sampled by predict / played per draw by backtest (0: predict prints the arg-max pick only)
+    temperature: float = 1.0  # Plackett-Luce weights exp(score / T); 0 = greedy (every ticket the arg-max pick)
+    seed: int = 0
+
+
+@dataclasses.dataclass
 class RunConfig:
     data: DataConfig = dataclasses.field(default_factory=DataConfig)
     gbdt: GBDTConfig = dataclasses.field(default_factory=GBDTConfig)
@@ -145,6 +152,7 @@ class RunConfig:
     dist: DistConfig = dataclasses.field(default_factory=DistConfig)
     ckpt: CkptConfig = dataclasses.field(default_factory=CkptConfig)
     log: LogConfig = dataclasses.field(default_factory=LogConfig)
+    tickets: TicketConfig = dataclasses.field(default_factory=TicketConfig)
     model: str = "gbdt"  # gbdt | rf | mlp | mlp-wide
     device: str = "auto"
     reference_compat: bool = False  # reproduce D-f (second booster trained on validation) + checkPredicts
@@ -264,6 +272,11 @@ def validate(cfg: RunConfig) -> RunConfig:
         raise ValueError(f"dist.comm_dtype={cfg.dist.comm_dtype!r}: must be fp32 or bf16")
     if cfg.dist.dp < 1 or cfg.dist.dp > 64:
         raise ValueError(f"dist.dp={cfg.dist.dp}: must be in 1..64 (ranks of one node)")
+    t = cfg.tickets
+    if not 0 <= t.n <= 64:
+        raise ValueError(f"tickets.n={t.n}: must be in 0..64")
+    if not (t.temperature >= 0 and t.temperature != float("inf")):
+        raise ValueError(f"tickets.temperature={t.temperature}: must be finite and >= 0 (0 = greedy)")
     if cfg.data.source == "device" and not cfg.data.n_draws and cfg.data.device_gb <= 0:
         raise ValueError("data.source=device needs data.n_draws or data.device_gb")
     return cfg

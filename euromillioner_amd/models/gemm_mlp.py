@@ -430,6 +430,15 @@ class GemmMLPTrainer:
         out["count"] = int(tot[7])
         return out
 
+    def backtest(self, masks, B: int, n_tickets: int, temperature: float = 1.0, seed: int = 0, offset: int = 0,
+                 sidx=None, chunk: int = 1 << 16) -> dict:
+        """Prize-tier counts of ``n_tickets`` sampled tickets on each of B samples (``ops.tickets.backtest_model``);
+        with ``lags > 1`` sample i is scored against draw i + lags, as :meth:`evaluate` does."""
+        from ..ops import tickets as OT
+
+        return OT.backtest_model(self, masks, B, n_tickets, temperature, seed, offset=offset, sidx=sidx, chunk=chunk,
+                                 target_masks=self._tmasks(masks))
+
     # ------------------------------------------------------------------ state
     def _logical(self, flat: torch.Tensor, flat_layer0: bool = False) -> dict[str, torch.Tensor]:
         """Views of the logical weights.  Layer 0's weight is the view [N, lags, 62] of its padded

@@ -287,6 +287,25 @@ class FusedSmallMLP:
         out["count"] = int(tot[7])
         return out
 
+    def tickets(self, draws: torch.Tensor, B: int, n_tickets: int, temperature: float = 1.0, seed: int = 0,
+                offset: int = 0, sidx=None, row_base: int = 0) -> torch.Tensor:
+        """``n_tickets`` tickets per sample, sampled from this model's logits (``ops.tickets.draw_tickets``):
+        int64 [B, n_tickets] feature masks.  Under ``bce`` the sampling weights exp(logit) are the odds."""
+        from ..ops import tickets as OT
+
+        if self.group is not None:
+            raise ValueError("tickets is single-process (no process group)")
+        lg = self.logits(draws, B, offset=offset, sidx=sidx)
+        return OT.draw_tickets(lg, B, n_tickets, temperature, seed, offset=offset, sidx=sidx,
+                               row_base=row_base)["tickets"]
+
+    def backtest(self, draws: torch.Tensor, B: int, n_tickets: int, temperature: float = 1.0, seed: int = 0,
+                 offset: int = 0, sidx=None, chunk: int = 1 << 20) -> dict:
+        """Prize-tier counts of ``n_tickets`` sampled tickets on each of B samples (``ops.tickets.backtest_model``)."""
+        from ..ops import tickets as OT
+
+        return OT.backtest_model(self, draws, B, n_tickets, temperature, seed, offset=offset, sidx=sidx, chunk=chunk)
+
     # ------------------------------------------------------------------ state
     def state_dict(self) -> dict[str, torch.Tensor]:
         return {k: v.detach().clone().cpu() for k, v in self.FM.unflatten(self.params).items()}

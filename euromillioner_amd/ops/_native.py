@@ -57,6 +57,9 @@ _SIGS = {
     "em_rows_to_masks": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p]),
     "em_gen_masks": (_i32, [ctypes.c_uint64, ctypes.c_uint32, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
     "em_gen_masks_at": (_i32, [ctypes.c_uint64, ctypes.c_uint32, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
+    "em_ticket_blocks": (_i32, [_i64, _i32]),
+    "em_draw_tickets": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _i64, _i64, _i64, _i32, _f32, ctypes.c_uint64,
+                               _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 

@@ -1,4 +1,4 @@
-"""``euromillioner train`` / ``predict`` (T5 trainers, T6 checkpoints, T4 data parallelism).
+"""``euromillioner train`` / ``predict`` / ``backtest`` (T5 trainers, T6 checkpoints, T4 data parallelism).
 
 The reference has exactly one "training" call site — ``XGBoost.train`` x2 in
 ``Main.java:128-138`` — and no MLP/RF/DP at all; the north star adds them
@@ -664,4 +664,98 @@ def predict_next(cfg: RunConfig) -> dict:
            "next_draw_date": date_str(nxt) if nxt is not None else None, "main": main, "stars": stars,
            "p_main": [round(float(p[i - 1]), 5) for i in main], "p_stars": [round(float(p[49 + s]), 5) for s in stars]}
     print(" ".join(f"{v:02d}" for v in main) + "  *  " + " ".join(f"{v:02d}" for v in stars))
+    tc = cfg.tickets
+    if tc.n > 0:
+        # through the numpy specification (one row): CPU and GPU boxes print the same tickets.  Scores: an
+        # MLP's logits (under bce the sampling weights are the odds), log p for the tree models
+        from . import tickets as TK
+
+        score = z.numpy().astype(np.float64) if kind == "mlp" else TK.log_scores(p)
+        tks, _ = TK.sample_tickets_py(score[None, :62], [len(ds) - 1], tc.n, tc.temperature, tc.seed)
+        res["tickets"] = []
+        for t in tks[0]:
+            tm, ts = TK.ticket_numbers(t)
+            res["tickets"].append({"main": tm, "stars": ts})
+            print(" ".join(f"{v:02d}" for v in tm) + "  *  " + " ".join(f"{v:02d}" for v in ts))
+        res["ticket_sampling"] = {"n": tc.n, "temperature": tc.temperature, "seed": tc.seed}
     return res
+
+
+def _backtest_numpy(net, ds, lags: int, margin: int, n_samples: int, tc, chunk: int = 1 << 14):
+    """DrawMLP logits + the numpy specification (the --device cpu path; row id = sample index, as on the GPU)."""
+    from . import tickets as TK
+    from .data.draws import mask_bits
+
+    X, _ = lag_features(ds.numbers, lags)
+    targets = mask_bits(ds.numbers)[lags:]  # sample i is scored against draw i + lags
+    hist, best = np.zeros((6, 3), dtype=np.int64), np.zeros(14, dtype=np.int64)
+    for a in range(margin, n_samples, chunk):
+        b = min(a + chunk, n_samples)
+        with torch.no_grad():
+            z = net(torch.from_numpy(X[a:b])).numpy()
+        tks, _ = TK.sample_tickets_py(z, np.arange(a, b), tc.n, tc.temperature, tc.seed)
+        h, bt = TK.score_tickets_py(tks, targets[a:b])
+        hist += h
+        best += bt
+    return hist, best
+
+
+def backtest(cfg: RunConfig) -> dict:
+    """``euromillioner backtest``: play ``tickets.n`` sampled tickets on every draw of the positional validation
+    split and count prize tiers, next to the expectation of uniformly random play.  MLP checkpoints only; on a
+    GPU the logits and the tickets never leave the device (csrc/tickets.hip), on ``--device cpu`` the same
+    numbers come from DrawMLP and the numpy specification."""
+    from . import tickets as TK
+    from .models.mlp import DrawMLP
+    from .ops.tickets import backtest_result
+
+    path = cfg.ckpt.resume or cfg.ckpt.path
+    if not path:
+        raise ValueError("backtest needs --ckpt pointing at an MLP checkpoint")
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    if path.endswith((".npz", ".json")):
+        raise ValueError("backtest covers MLP checkpoints (predict --tickets samples from RF / GBDT models)")
+    tc = cfg.tickets
+    if tc.n < 1:
+        raise ValueError("backtest needs --tickets N with N in 1..64")
+    ck = load_mlp_checkpoint(path)
+    sizes, ex = tuple(ck["sizes"]), ck["extra"]
+    lags = int(ex.get("lags", sizes[0] // 62))
+    act, loss = ex.get("activation", "relu"), ex.get("loss", "softmax")
+    ds = load_draws(cfg)
+    n_samples = len(ds) - lags
+    margin = positional_split(n_samples, cfg.data.train_pct)
+    rows = n_samples - margin
+    if rows < 1:
+        raise ValueError("empty validation split")
+    use_gpu = cfg.device == "cuda" or (cfg.device == "auto" and torch.cuda.is_available())
+    if use_gpu:
+        from .models.mlp import FusedSmallMLP
+
+        if sizes == (62, 128, 62) and act == "relu":
+            model = FusedSmallMLP("cuda", loss=loss, dtype=cfg.mlp.dtype,
+                                  state_dict={_FusedEngine._MAP[k]: v for k, v in ck["state_dict"].items()})
+        else:
+            from .models.gemm_mlp import GemmMLPTrainer
+
+            model = GemmMLPTrainer(sizes, "cuda", activation=act, loss=loss, state_dict=ck["state_dict"],
+                                   dtype=cfg.mlp.dtype, lags=lags)
+        masks = FusedSmallMLP.prepare(torch.from_numpy(ds.numbers).cuda())
+        r = model.backtest(masks, rows, tc.n, tc.temperature, tc.seed, offset=margin)
+        engine = "hip"
+    else:
+        net = DrawMLP(sizes, activation=act, loss=loss, use_hip=False)
+        net.load_state_dict(ck["state_dict"])
+        r = backtest_result(*_backtest_numpy(net, ds, lags, margin, n_samples, tc), rows, tc.n)
+        engine = "numpy"
+    tiers, exp_t = TK.tier_counts(r["hist"]), r["uniform"]["tiers"]
+    print(f"{rows} draws x {tc.n} tickets (T={tc.temperature:g}, seed {tc.seed}): tickets per prize tier | "
+          f"draws by best ticket (uniform play beside each)")
+    for k in range(13):
+        print(f"{k + 1:>2} {TK.TIER_NAMES[k]:>4} {int(tiers[k]):>12} {exp_t[k]:>14.3f} | "
+              f"{int(r['best'][k]):>12} {r['uniform']['best'][k]:>14.3f}")
+    return {"model": "mlp", "checkpoint": path, "engine": engine, "sizes": list(sizes), "rows": rows,
+            "tickets": r["tickets"], "n_tickets": tc.n, "temperature": tc.temperature, "seed": tc.seed,
+            "hist": r["hist"].tolist(), "best": r["best"].tolist(), "tiers": tiers.tolist(),
+            "uniform": {k: np.asarray(v).tolist() for k, v in r["uniform"].items()}}
