@@ -407,6 +407,7 @@ class GBDT:
         self.num_feature = None
         self.n_tasks = 1
         self.history: list[dict] = []
+        self.train_history: list[float] = []  # the eval metric on the training rows after each round
 
     @classmethod
     def from_params(cls, params: dict, nround: int = 500, **kw):
@@ -444,7 +445,10 @@ class GBDT:
 
     def fit(self, X: np.ndarray, Y: np.ndarray, evals: dict | None = None, group=None):
         """``group``: a torch.distributed process group -> data-parallel boosting (C4): X/Y and every
-        eval set are this rank's row shard; histograms, node sums and metrics are all-reduced."""
+        eval set are this rank's row shard; histograms, node sums and metrics are all-reduced.
+
+        ``history`` gets one record per round with the metric of every eval set, ``train_history`` the metric
+        on the training rows after each round (empty under data parallelism, which does not compute it)."""
         X = np.asarray(X, dtype=np.float64)
         Y = np.asarray(Y, dtype=np.float64)
         dp = _DP(group) if group is not None else None
@@ -469,6 +473,7 @@ class GBDT:
         bins = apply_bins(X, self.cuts)
         nbins = max((len(c) for c in self.cuts), default=0) + 1
         evals = evals or {}
+        self.train_history = []
         backend = self._resolve_backend()
         self.backend_used = backend
         if backend == "hip":
@@ -606,6 +611,8 @@ class GBDT:
             for name, (ex, ey) in evals.items():
                 rec[name] = self._metric(np.asarray(ey, np.float64).reshape(len(ex), -1), ev_margin[name], dp)
             hist.append(rec)
+            if dp is None:  # (the data-parallel engines keep no train metric: train_history stays empty)
+                self.train_history.append(float(self._metric(Y, margin)))
             self._log_round(rec)
         return trees, hist
 

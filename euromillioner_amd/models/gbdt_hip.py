@@ -65,6 +65,9 @@ class _Cells:
 
 
 def fit(model, X, bins, nbins, Y, evals, rounds_per_call: int = 500, dp=None):
+    """Returns (trees, history).  ``model.train_history`` gets the eval metric on the training rows after
+    each round (R floats, column 0 of the driver's per-round metric table).  The data-parallel path does
+    not compute that column: there ``train_history`` stays empty."""
     dev = _dev()
     n, F = bins.shape
     T = Y.shape[1]
@@ -107,6 +110,7 @@ def fit(model, X, bins, nbins, Y, evals, rounds_per_call: int = 500, dp=None):
     cover = torch.zeros_like(leaf)
     hist = torch.zeros(R * (1 + len(ev_names)), dtype=torch.float32, device=dev)
     history = []
+    model.train_history = []
     if dp is not None:
         _fit_dp_rounds(model, dp, d_bins, d_Y, n, F, cells, T, margin, ev_names, ev_keep, g, h, node, partial, Gs, Hs,
                        mpart, status, feat, sbin, leaf, gain, cover, history, stream)
@@ -133,6 +137,7 @@ def fit(model, X, bins, nbins, Y, evals, rounds_per_call: int = 500, dp=None):
             for j, name in enumerate(ev_names):
                 rec[name] = float(hh[i, 1 + j])
             history.append(rec)
+            model.train_history.append(float(hh[i, 0]))
             model._log_round(rec)
         r0 = r1
     # the host copy of the ensemble: dtypes converted on the device, one packed device-to-host copy,
