@@ -9,6 +9,7 @@ runs the whole pipeline (``Main.java:35``).  Here:
     euromillioner train --model mlp-wide | rf | gbdt
     euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv] [--tickets 5 --temperature 1.0]
     euromillioner backtest --ckpt model.zip --tickets 16   # prize tiers of sampled tickets on the validation split
+    euromillioner explain --ckpt model.json [--top 3]      # which of the last draw's numbers push each GBDT pick (TreeSHAP)
     euromillioner gen --n 1000000 --planted 0.9 --out draws.csv
     euromillioner info                 # device, native libraries, kernel inventory
 
@@ -90,6 +91,9 @@ def build_parser() -> argparse.ArgumentParser:
     p = sub.add_parser("backtest", help="play sampled tickets on every validation draw and count prize tiers")
     _add_common(p)
     p.add_argument("--model", default=None, choices=["mlp", "mlp-wide"])
+    p = sub.add_parser("explain", help="TreeSHAP: the features behind each number a GBDT checkpoint picks")
+    _add_common(p)
+    p.add_argument("--top", type=int, default=3, help="features listed per picked number")
     p = sub.add_parser("gen", help="write synthetic draws to CSV")
     p.add_argument("--n", "--n-draws", dest="n", type=int, default=None, help="draws to generate (same name as train --n-draws)")
     p.add_argument("--seed", type=int, default=0)
@@ -156,6 +160,10 @@ def main(argv=None) -> int:
             from .train import backtest
 
             res = backtest(cfg)
+        elif a.cmd == "explain":
+            from .train import explain_next
+
+            res = explain_next(cfg, top=a.top)
         else:
             ap.print_help()
             return 2

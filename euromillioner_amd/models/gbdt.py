@@ -428,9 +428,8 @@ class GBDT:
     def base_margin(self) -> float:
         return base_margin_for(self.objective, self.base_score)
 
-    def _resolve_backend(self):
-        if self.backend != "auto":
-            return self.backend
+    @staticmethod
+    def _auto_backend() -> str:
         try:
             import torch
 
@@ -442,6 +441,9 @@ class GBDT:
         except Exception:  # noqa: BLE001
             pass
         return "numpy"
+
+    def _resolve_backend(self):
+        return self.backend if self.backend != "auto" else self._auto_backend()
 
     def fit(self, X: np.ndarray, Y: np.ndarray, evals: dict | None = None, group=None):
         """``group``: a torch.distributed process group -> data-parallel boosting (C4): X/Y and every
@@ -665,6 +667,75 @@ class GBDT:
         if self.objective == "multi:softmax":
             return np.argmax(p, axis=1).astype(np.float32)
         return p
+
+    # ------------------------------------------------------------------ explanations
+    def _explain_backend(self, backend):
+        be = backend or getattr(self, "backend_used", "numpy")  # as predict_margin: a loaded model is "numpy"
+        if be == "auto":  # the device when there is one
+            be = self._auto_backend()
+        if be not in ("hip", "numpy"):
+            raise ValueError("backend must be 'auto', 'hip' or 'numpy'")
+        return be
+
+    def predict_contribs(self, X: np.ndarray, backend: str | None = None, iteration_range=None,
+                         chunk_rows: int | None = None) -> np.ndarray:
+        """Like ``Booster.predict(pred_contribs=True)``: float32 ``[n, T, F+1]`` path-dependent TreeSHAP
+        contributions to the margin of every task (``multi:*``: T = num_class); the last column is the bias,
+        and ``sum(axis=2) == predict_margin``.  ``iteration_range=(r0, r1)`` keeps the trees of rounds
+        ``[r0, r1)``.  The HIP path scores ``chunk_rows`` rows per launch (the result does not depend on it);
+        a model outside its plan (``max_depth > 8``, too many features for the LDS tile) runs on the numpy
+        path unless ``backend="hip"`` was asked for explicitly (``backend="auto"``: the device if there is one).  Works on fitted and on loaded models."""
+        from . import gbdt_explain as E
+
+        if self._explain_backend(backend) == "hip":
+            from . import gbdt_hip
+
+            try:
+                return gbdt_hip.predict_contribs(self, X, iteration_range, chunk_rows)
+            except gbdt_hip.PlanUnsupported as e:
+                if backend == "hip":
+                    raise
+                from .. import log as L
+
+                L.get("GBDT").warning("%s; contributions on the numpy path", e)
+        return E.contribs_numpy(self, X, iteration_range).astype(np.float32)
+
+    def predict_leaf(self, X: np.ndarray, backend: str | None = None) -> np.ndarray:
+        """Like ``Booster.predict(pred_leaf=True)``: int32 ``[n, n_trees]``, the node where each row's walk
+        stops in each tree (tree ``k`` belongs to task ``k % T``).  The entries are HEAP indices (root 0,
+        children of ``i`` at ``2i+1`` / ``2i+2``), not XGBoost's node ids, which number the nodes in the
+        order they were created."""
+        from . import gbdt_explain as E
+
+        if self._explain_backend(backend) == "hip":
+            from . import gbdt_hip
+
+            try:
+                return gbdt_hip.predict_leaf(self, X)
+            except gbdt_hip.PlanUnsupported:
+                if backend == "hip":
+                    raise
+        return E.leaf_index_numpy(self, X)
+
+    def get_score(self, importance_type: str = "weight", per_task: bool = False):
+        """Like ``Booster.get_score``: ``{"f3": value}`` over the features the trees split on (summed over the
+        tasks; ``gain`` / ``cover`` are averages per split), or, with ``per_task``, a float64 ``[T, F]`` array.
+        ``importance_type``: weight | gain | cover | total_gain | total_cover."""
+        from . import gbdt_explain as E
+
+        F = E.num_features(self)
+        if importance_type not in E.IMPORTANCE_TYPES:
+            raise ValueError(f"importance_type must be one of {E.IMPORTANCE_TYPES}")
+        if per_task:
+            return E.importance(self.trees, self.n_tasks, F, importance_type)
+        weight = E.importance(self.trees, self.n_tasks, F, "weight").sum(axis=0)
+        if importance_type == "weight":
+            val = weight
+        else:
+            val = E.importance(self.trees, self.n_tasks, F, "total_" + importance_type.split("_")[-1]).sum(axis=0)
+            if not importance_type.startswith("total_"):
+                val = np.divide(val, weight, out=np.zeros_like(val), where=weight > 0)
+        return {f"f{f}": float(val[f]) for f in range(F) if weight[f] > 0}
 
     # ------------------------------------------------------------------ persistence
     def to_json(self) -> dict:

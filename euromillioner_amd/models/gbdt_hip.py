@@ -33,6 +33,11 @@ N.register_signatures({
     "em_gbdt_dp_level_split": (_i, [_i, _v, _v, _i, _i, _i, _v, _i, _i, _v, _v, _v, _v, _v, _v, _v, _f, _f, _v]),
     "em_gbdt_dp_round_end": (_i, [_i, _i, _i, _v, _v, _v, _v, _v, _v, _v, _v, _v, _f, _f, _f, _v]),
     "em_gbdt_metric_sum": (_i, [_v, _v, _i, _i, _i, _i, _v, _v, _v]),
+    # csrc/gbdt_shap.hip
+    "em_gbdt_shap_lds_bytes": (_i, [_i, _i]),
+    "em_gbdt_shap_paths": (_i, [_i, _i, _i, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v]),
+    "em_gbdt_shap": (_i, [_v, _i, _i, _i, _i, _i, _i, _i, ctypes.c_double, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v]),
+    "em_gbdt_leaf_index": (_i, [_v, _v, _i, _i, _i, _i, _v, _v, _v, _v]),
 })
 
 OBJ = {"reg:logistic": 0, "binary:logistic": 0, "reg:squarederror": 1, "multi:softprob": 2, "multi:softmax": 2}
@@ -158,6 +163,7 @@ def fit(model, X, bins, nbins, Y, evals, rounds_per_call: int = 500, dp=None):
         raise RuntimeError("GPU GBDT: a fused level's wait for its task's splits timed out (trees invalid)")
     trees = TreeArrays.from_arrays(D, st, fe, sb, lf, gn, cv)
     model._device_trees = (status, feat, sbin, leaf)
+    model._device_cover = cover  # beside them for the explanations (predict_contribs)
     return trees, history
 
 
@@ -232,3 +238,130 @@ def predict_margin(model, X):
     N.call("em_gbdt_predict", d_bins.data_ptr(), margin.data_ptr(), T, n, F, tr.max_depth, 0, tr.n_trees,
            status.data_ptr(), feat.data_ptr(), sbin.data_ptr(), leaf.data_ptr(), N.stream_handle(dev))
     return margin.view(T, n).t().cpu().numpy().astype(np.float64)
+
+
+# ----------------------------------------------------------------------------- explanations (csrc/gbdt_shap.hip)
+SHAP_CHUNK_BYTES = 256 << 20  # default chunk_rows: at most this much contribution output per launch
+
+
+def _explain_trees(model, sbin_host):
+    """(status, feat, sbin, leaf, cover) on the device: what ``fit`` left there, or copies of the host trees
+    (a loaded checkpoint, a numpy fit) with the given ``sbin``."""
+    dt, cv = getattr(model, "_device_trees", None), getattr(model, "_device_cover", None)
+    if dt is not None and cv is not None and model.cuts is not None:
+        return (*dt, cv)
+    cached = getattr(model, "_explain_device", None)
+    if cached is not None and cached[0] is model.trees:
+        return cached[1]
+    dev, tr = _dev(), model.trees
+    arrs = (torch.from_numpy(np.ascontiguousarray(tr.status, dtype=np.int8).reshape(-1)).to(dev),
+            torch.from_numpy(tr.feat.astype(np.int16).reshape(-1)).to(dev),
+            torch.from_numpy(np.asarray(sbin_host).astype(np.uint8).reshape(-1)).to(dev),
+            torch.from_numpy(tr.leaf.astype(np.float32).reshape(-1)).to(dev),
+            torch.from_numpy(tr.cover.astype(np.float32).reshape(-1)).to(dev))
+    model._explain_device = (tr, arrs)
+    return arrs
+
+
+def _explain_plan(model, need_lds: bool):
+    """Validate the trees on the host (the kernels index ``bins`` by ``feat``) and check the plan; returns
+    (cuts, device trees, F)."""
+    from . import gbdt_explain as E
+
+    tr = model.trees
+    F = E.num_features(model)
+    E.validate_trees(tr, F)
+    cuts, sbin_host = E.model_bins(model)
+    if any(len(c) > 255 for c in cuts):
+        raise PlanUnsupported("GPU GBDT supports at most 256 bins per feature")
+    if F > 32767:
+        raise PlanUnsupported("GPU GBDT explanations index features with 16 bits")
+    if need_lds and N.query("em_gbdt_shap_lds_bytes", F, tr.max_depth) < 0:
+        raise PlanUnsupported(f"GPU TreeSHAP: no plan for max_depth {tr.max_depth} with {F} features (the plan covers "
+                              f"max_depth <= 8 and a row tile, 324 bytes per feature, within 160 KB of LDS)")
+    if not need_lds and not 1 <= tr.max_depth <= 12:
+        raise PlanUnsupported(f"GPU leaf index: max_depth {tr.max_depth} outside [1, 12]")
+    return cuts, _explain_trees(model, sbin_host), F
+
+
+def _bins_for(model, X, cuts, F):
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != F:
+        raise ValueError(f"X must be [n, {F}], got {X.shape}")
+    return np.ascontiguousarray(apply_bins(X, cuts), dtype=np.uint8)
+
+
+def _shap_tables(model, dtrees, F):
+    """The device path table of every tree (em_gbdt_shap_paths), built once per set of device trees."""
+    cached = getattr(model, "_shap_paths", None)
+    if cached is not None and cached[0] is dtrees[0]:
+        return cached[1]
+    dev = dtrees[0].device
+    tr = model.trees
+    K, D = tr.n_trees, tr.max_depth
+    E_ = K * (2 ** (D + 1) - 1)
+    pd = torch.empty(E_, dtype=torch.int32, device=dev)
+    pleaf = torch.empty(E_, dtype=torch.float32, device=dev)
+    pf, plo, phi = (torch.empty(E_ * D, dtype=torch.int32, device=dev) for _ in range(3))
+    pz = torch.empty(E_ * D, dtype=torch.float32, device=dev)
+    pbias = torch.empty(E_, dtype=torch.float64, device=dev)
+    status, feat, sbin, leaf, cover = dtrees
+    N.call("em_gbdt_shap_paths", K, D, F, status.data_ptr(), feat.data_ptr(), sbin.data_ptr(), leaf.data_ptr(),
+           cover.data_ptr(), pd.data_ptr(), pleaf.data_ptr(), pf.data_ptr(), plo.data_ptr(), phi.data_ptr(), pz.data_ptr(),
+           pbias.data_ptr(), N.stream_handle(dev))
+    tables = (pd, pleaf, pf, plo, phi, pz, pbias)
+    model._shap_paths = (dtrees[0], tables)
+    return tables
+
+
+def predict_contribs(model, X, iteration_range=None, chunk_rows=None):
+    """float32 [n, T, F+1] (GBDT.predict_contribs).  Rows go through the kernel ``chunk_rows`` at a time, so the
+    [T, chunk, F+1] device output is bounded; a row's result depends on the row only."""
+    from . import gbdt_explain as E
+
+    cuts, dtrees, F = _explain_plan(model, need_lds=True)
+    bins = _bins_for(model, X, cuts, F)
+    k0, k1 = E._tree_range(model, iteration_range)
+    n, T, tr = bins.shape[0], model.n_tasks, model.trees
+    out = np.empty((n, T, F + 1), dtype=np.float32)
+    if n == 0:
+        return out
+    if chunk_rows is None:
+        chunk_rows = max(256, SHAP_CHUNK_BYTES // (T * (F + 1) * 4) // 256 * 256)
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("chunk_rows must be positive")
+    chunk_rows = min(chunk_rows, ((1 << 31) - 1) // F)
+    dev = dtrees[0].device
+    tables = _shap_tables(model, dtrees, F)
+    bias = torch.empty(T, dtype=torch.float32, device=dev)
+    stream = N.stream_handle(dev)
+    for a in range(0, n, chunk_rows):
+        b = min(n, a + chunk_rows)
+        d_bins = torch.from_numpy(bins[a:b]).to(dev)
+        d_out = torch.empty((T, b - a, F + 1), dtype=torch.float32, device=dev)
+        N.call("em_gbdt_shap", d_bins.data_ptr(), b - a, F, T, tr.max_depth, tr.n_trees, k0, k1, float(model.base_margin),
+               *(t.data_ptr() for t in tables), bias.data_ptr(), d_out.data_ptr(), stream)
+        out[a:b] = d_out.permute(1, 0, 2).cpu().numpy()
+    return out
+
+
+def predict_leaf(model, X):
+    """int32 [n, n_trees] heap indices (GBDT.predict_leaf)."""
+    cuts, dtrees, F = _explain_plan(model, need_lds=False)
+    bins = _bins_for(model, X, cuts, F)
+    n, tr = bins.shape[0], model.trees
+    if n == 0 or tr.n_trees == 0:
+        return np.zeros((n, tr.n_trees), dtype=np.int32)
+    dev = dtrees[0].device
+    status, feat, sbin = dtrees[:3]
+    rows = max(1, SHAP_CHUNK_BYTES // (4 * tr.n_trees))
+    out = np.empty((n, tr.n_trees), dtype=np.int32)
+    for a in range(0, n, rows):
+        b = min(n, a + rows)
+        d_bins = torch.from_numpy(bins[a:b]).to(dev)
+        d_out = torch.empty((b - a, tr.n_trees), dtype=torch.int32, device=dev)
+        N.call("em_gbdt_leaf_index", d_bins.data_ptr(), d_out.data_ptr(), b - a, F, tr.max_depth, tr.n_trees,
+               status.data_ptr(), feat.data_ptr(), sbin.data_ptr(), N.stream_handle(dev))
+        out[a:b] = d_out.cpu().numpy()
+    return out

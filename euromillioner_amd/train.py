@@ -681,6 +681,57 @@ def predict_next(cfg: RunConfig) -> dict:
     return res
 
 
+def gbdt_feature_names(n_features: int) -> list[str]:
+    """Names of the next-draw GBDT's input columns: the 50 numbers and 12 stars of the last draw, then its date
+    fields (``pipeline.gbdt_dataset``)."""
+    names = [f"number {i + 1}" for i in range(50)] + [f"star {i + 1}" for i in range(12)]
+    names += ["weekday", "month", "day", "year"]
+    return (names + [f"f{i}" for i in range(len(names), n_features)])[:n_features]
+
+
+def explain_next(cfg: RunConfig, top: int = 3) -> dict:
+    """``euromillioner explain``: for each number and star a GBDT checkpoint picks for the next draw, the ``top``
+    features of the last draw with the largest |TreeSHAP contribution| to that pick's margin."""
+    path = cfg.ckpt.resume or cfg.ckpt.path
+    if not path:
+        raise ValueError("explain needs --ckpt (or --resume) pointing at a GBDT checkpoint")
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    if not path.endswith(".json"):
+        raise ValueError(f"explain covers GBDT checkpoints (.json) only, not {os.path.basename(path)}")
+    if top < 1:
+        raise ValueError("--top must be at least 1")
+    from .models.gbdt import GBDT
+    from .models.gbdt_explain import num_features
+    from .pipeline import _gbdt_backend
+
+    ds = load_draws(cfg)
+    g = GBDT.load(path)
+    if g.n_tasks != 62:
+        raise ValueError(f"explain needs a next-draw GBDT (62 boosters), this checkpoint has {g.n_tasks}")
+    nf = num_features(g)
+    x = multi_hot(ds.numbers[-1:]).astype(np.float64)
+    if nf > 62 and ds.dates is not None:
+        from .data.draws import featurize_raw
+
+        x = np.concatenate([x, featurize_raw(ds)[-1:, :4].astype(np.float64)], axis=1)
+    if x.shape[1] != nf:
+        raise ValueError(f"the checkpoint expects {nf} features, the data gives {x.shape[1]}")
+    be = g._explain_backend(_gbdt_backend(cfg))
+    phi = np.asarray(g.predict_contribs(x, backend=be), dtype=np.float64)[0]  # [62, F+1]
+    main, stars = _top_pick(phi.sum(axis=1))  # sum == margin; the logistic transform keeps the order
+    names = gbdt_feature_names(nf)
+    picks = []
+    for kind, v, t in [("number", v, v - 1) for v in main] + [("star", v, 49 + v) for v in stars]:
+        order = np.argsort(-np.abs(phi[t, :nf]), kind="stable")[:top]
+        feats = [{"feature": names[f], "index": int(f), "phi": round(float(phi[t, f]), 6)} for f in order]
+        picks.append({"pick": f"{kind} {v}", "margin": round(float(phi[t].sum()), 6), "bias": round(float(phi[t, nf]), 6),
+                      "top": feats})
+        print(f"{kind} {v:02d}: " + ", ".join(f"{d['feature']} {d['phi']:+.4f}" for d in feats))
+    return {"model": "gbdt", "checkpoint": path, "backend": be, "main": main, "stars": stars,
+            "after_draw": date_str(ds.dates[-1]) if ds.dates is not None else None, "explain": picks}
+
+
 def _backtest_numpy(net, ds, lags: int, margin: int, n_samples: int, tc, chunk: int = 1 << 14):
     """DrawMLP logits + the numpy specification (the --device cpu path; row id = sample index, as on the GPU)."""
     from . import tickets as TK
