@@ -154,6 +154,12 @@ __global__ void gbdt_round_start(int8_t* __restrict__ st, int16_t* __restrict__ 
   }
 }
 
+// leaf value -G / (H + lambda) * eta; a node with H + lambda <= 0 (lambda = 0 and every row of the tree
+// dropped by the subsample) gets 0 as in XGBoost's CalcWeight, not 0 / 0
+EM_DEVICE float leaf_weight(double G, double H, double lam, double eta) {
+  return H + lam > 0.0 ? (float)(-G / (H + lam) * eta) : 0.f;
+}
+
 EM_DEVICE int leaf_ancestor(const int8_t* st, int nd);
 EM_DEVICE double metric_term(float m, float y, int obj, int metric);
 
@@ -1030,7 +1036,9 @@ EM_DEVICE void split_body(int vb, char* smem, const A* __restrict__ hist, int nc
     auto cand = [&](int f, int b, A GLa, A HLa) {  // candidate "bin <= b" of feature f
       const double GL = val(GLa), HL = val(HLa);
       const double GR = val(Gna - GLa), HR = val(Hna - HLa);
-      if (HL >= mcw && HR >= mcw) {
+      // a side with H + lambda <= 0 (an empty side at lambda = 0) is no candidate: XGBoost's CalcGain gives
+      // such a side 0, so the split never exceeds KRT_EPS there; said here instead of left to NaN > best
+      if (HL >= mcw && HR >= mcw && HL + lam > 0.0 && HR + lam > 0.0) {
         const double gn = GL * GL / (HL + lam) + GR * GR / (HR + lam) - root;
         if (gn > best) {  // strict: candidates come in ascending (feature, bin) order per thread
           best = gn;
@@ -1213,7 +1221,7 @@ EM_DEVICE void split_body(int vb, char* smem, const A* __restrict__ hist, int nc
   for (int k = threadIdx.x; k < NN; k += blockDim.x) {
     st[k] = sst[k];
     feat[o + k] = sfe[k];
-    fin.leaf[o + k] = sst[k] == 2 ? (float)(-sG[k] / (sH[k] + lam) * fin.eta) : 0.f;
+    fin.leaf[o + k] = sst[k] == 2 ? leaf_weight(sG[k], sH[k], lam, fin.eta) : 0.f;
     fin.cover[o + k] = sst[k] ? (float)sH[k] : 0.f;
   }
   GSTAMP(16 * level + 5);
@@ -1263,7 +1271,7 @@ __global__ void gbdt_finalize(int T, int NN, int max_depth, int8_t* __restrict__
   int8_t* st = status + o;
   prune_task(st, feat + o, gain + o, max_depth, gamma);
   for (int i = 0; i < NN; ++i) {
-    leaf[o + i] = st[i] == 2 ? (float)(-G[o + i] / (H[o + i] + lam) * eta) : 0.f;
+    leaf[o + i] = st[i] == 2 ? leaf_weight(G[o + i], H[o + i], lam, eta) : 0.f;
     cover[o + i] = st[i] ? (float)H[o + i] : 0.f;
   }
 }

@@ -28,7 +28,12 @@ Semantics implemented (XGBoost 1.x ``ColMaker`` + ``TreePruner``):
   loss_chg < gamma (``min_split_loss``);
 * leaf value = -G/(H+l) * eta; margins start at logit(base_score);
 * reg:logistic/binary:logistic: g = p - y, h = max(p(1-p), 1e-16), labels must be
-  in [0, 1] (XGBoost raises otherwise); reg:squarederror: g = m - y, h = 1.
+  in [0, 1] (XGBoost raises otherwise); reg:squarederror: g = m - y, h = 1;
+* a side with H + l <= 0 (an empty side at l = 0) is no split candidate and a leaf with H + l <= 0 is 0
+  (XGBoost's CalcGain / CalcWeight), so ``reg_lambda = 0, min_child_weight = 0`` grows past empty bins;
+* subsample < 1 drops the gradient pair of element (round, task, row) by a counter hash
+  (:func:`subsample_keep`, ``hash3`` in ``csrc/gbdt.hip``), not by a generator state: both engines draw the
+  same mask from ``seed``, so they grow the same trees (XGBoost's own draws are not reproduced).
 
 Multiple targets (``Y [n, T]``) train T independent boosters in lock-step (the
 default "next-draw" task: one booster per number/star, 62 in all).
@@ -245,6 +250,35 @@ def gradients(objective: str, margin: np.ndarray, y: np.ndarray):
     raise ValueError(f"unsupported objective {objective}")
 
 
+# ----------------------------------------------------------------------------- row subsampling
+def _hash3(a, b, c) -> np.ndarray:
+    """csrc/gbdt.hip hash3 on uint32 arrays (every product and sum wraps modulo 2^32)."""
+    u = np.uint32
+    a, b, c = (np.asarray(v).astype(np.uint32) for v in (a, b, c))
+    with np.errstate(over="ignore"):
+        h = (a * u(0x9E3779B1)) ^ ((b + u(0x7F4A7C15)) * u(0x85EBCA77)) ^ ((c + u(0x165667B1)) * u(0xC2B2AE3D))
+        h = h ^ (h >> u(15))
+        h = h * u(0x2C1B3C6D)
+        h = h ^ (h >> u(12))
+        h = h * u(0x297A2D39)
+        h = h ^ (h >> u(15))
+    return h
+
+
+def subsample_seed(seed: int, rank: int = 0) -> int:
+    """The 32-bit seed of the keep mask; every data-parallel rank mixes its rank in (its rows are its own)."""
+    return (int(seed) + 0x9E3779B9 * int(rank)) & 0xFFFFFFFF
+
+
+def subsample_keep(seed: int, rnd: int, n: int, T: int, subsample: float) -> np.ndarray:
+    """bool [n, T]: element (row r, task t) of round ``rnd`` keeps its gradient pair.  A counter hash, not a
+    generator state, so both engines drop the same elements (csrc/gbdt.hip grad_of): u = the top 24 bits of
+    hash3(seed, rnd * 131071 + t, r) as a fraction, kept iff u < float32(subsample)."""
+    ctr = (np.uint64(rnd) * np.uint64(131071) + np.arange(T, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
+    hsh = _hash3(np.uint32(seed & 0xFFFFFFFF), ctr.astype(np.uint32)[None, :], np.arange(n, dtype=np.uint32)[:, None])
+    return (hsh >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24) < np.float32(subsample)
+
+
 # ----------------------------------------------------------------------------- histogram modes
 HIST_MODES = ("auto", "exact", "quant")
 QUANT_MIN_ROWS = 32768  # "auto": fixed-point histograms from this many rows on (reference config: 928 rows -> exact)
@@ -307,9 +341,9 @@ def _best_split_hist(hg, hh, G, H, lam, mcw):
     if cg.size == 0:
         return None
     gr, hr = G - cg, H - ch
-    ok = (ch >= mcw) & (hr >= mcw)
-    root = G * G / (H + lam)
-    gain = np.where(ok, cg * cg / (ch + lam) + gr * gr / (hr + lam) - root, -np.inf)
+    ok = (ch >= mcw) & (hr >= mcw) & (ch + lam > 0) & (hr + lam > 0)  # (an empty side at lambda = 0: no candidate)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gain = np.where(ok, cg * cg / (ch + lam) + gr * gr / (hr + lam) - G * G / (H + lam), -np.inf)
     # first max in (feature, bin) order == lower feature index wins ties
     flat = int(np.argmax(gain))
     f, b = divmod(flat, gain.shape[1])
@@ -366,8 +400,8 @@ def _prune_and_leaves(trees: TreeArrays, k, G, H, lam, gamma, eta, max_depth):
                 trees.status[k, l] = trees.status[k, r] = 0
                 trees.feat[k, i] = -1
     for i in range(len(G)):
-        if trees.status[k, i] == 2:
-            trees.leaf[k, i] = np.float32(-G[i] / (H[i] + lam) * eta)  # leaf values are float (XGBoost)
+        if trees.status[k, i] == 2:  # leaf values are float (XGBoost); CalcWeight: 0 where H + lambda <= 0
+            trees.leaf[k, i] = np.float32(-G[i] / (H[i] + lam) * eta) if H[i] + lam > 0 else 0.0
 
 
 def _leaf_of(trees: TreeArrays, k, node):
@@ -519,7 +553,7 @@ class GBDT:
         row_feat = np.repeat(np.arange(F), nbf)
         rowseg_start = off[row_feat]
         valid_row = (np.arange(off[-1]) - rowseg_start) < (nbf[row_feat] - 1)  # not the last bin of a feature
-        rng = np.random.default_rng(self.seed if dp is None else [self.seed, dp.rank])
+        seed = subsample_seed(self.seed, dp.rank if dp is not None else 0)
         red = dp.sum_ if dp is not None else (lambda a: a)
         hist = []
         tix = np.arange(T)
@@ -529,7 +563,7 @@ class GBDT:
         for rnd in range(R):
             g, h = gradients(self.objective, margin, Y32)
             if self.subsample < 1.0:
-                keep = (rng.random((n, T)) < self.subsample).astype(np.float32)
+                keep = subsample_keep(seed, rnd, n, T, self.subsample).astype(np.float32)
                 g, h = g * keep, h * keep
             if qs:  # fixed point: integer sums, exact in any order (== gbdt_hist_q)
                 g64, h64 = _quantise(g, qs), _quantise_h(h, qs)
@@ -580,7 +614,10 @@ class GBDT:
                 else:
                     Gn, Hn = Gs[cols_t, cols_i], Hs[cols_t, cols_i]
                     GR, HR = Gn[None, :] - GL, Hn[None, :] - HL
-                ok = valid_row[:, None] & (HL >= self.mcw) & (HR >= self.mcw) & (st[cols_t, cols_i] == 2)[None, :]
+                # (a side with H + lambda <= 0, an empty side at lambda = 0, is no candidate: XGBoost's CalcGain
+                # gives it 0, so such a split never exceeds KRT_EPS; left in, its 0 / 0 would win the arg-max)
+                ok = valid_row[:, None] & (HL >= self.mcw) & (HR >= self.mcw) & (st[cols_t, cols_i] == 2)[None, :] & \
+                    (HL + self.lam > 0) & (HR + self.lam > 0)
                 with np.errstate(divide="ignore", invalid="ignore"):
                     gn = GL * GL / (HL + self.lam) + GR * GR / (HR + self.lam) - (Gn * Gn / (Hn + self.lam))[None, :]
                 gn = np.where(ok, gn, -np.inf)
