@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "draw_topk.h"
 
 namespace {
 
@@ -1233,6 +1234,245 @@ __global__ void __launch_bounds__(RFP_WAVES * 64) rf_predict_lds(const uint64_t*
   }
 }
 
+// K11-OOB: out-of-bag prediction.  Row i is out of bag for tree t when its bootstrap weight is 0, and the
+// weight is a pure function of (seed, global tree id, row): row_weight() == 0 <=> poisson1's m < th[0], so
+// the in-bag sets are recomputed here from the hash and nothing of the fit is stored.  Per row: the sum of
+// the leaf vectors of its out-of-bag trees (fp32, ascending tree order) over their count; rows without an
+// out-of-bag tree get zeros and count 0.  Outputs 62 / 63 are 0.  Two bit-identical forms, as K11.
+constexpr uint64_t RF_OOB_TH0 = 0xbc5ab1b16779cull;  // poisson1's th[0] = cdf(0) * 2^53
+// hash3(seed, 2^32 + tree, row) = mix64(key ^ row) with the tree's key = mix64(seed ^ mix64(2^32 + tree))
+EM_DEVICE uint64_t rf_oob_key(uint64_t seed, int tree) { return mix64(seed ^ mix64(0x100000000ull + (uint64_t)tree)); }
+EM_DEVICE bool rf_is_oob(uint64_t key, int64_t row) { return (mix64(key ^ (uint64_t)row) >> 11) < RF_OOB_TH0; }
+
+// General form (any W, any depth): one wavefront per row as rf_predict; lane l hashes and -- only when the
+// row is out of bag for it -- walks tree t0 + l, then lane j (= output j) gathers the out-of-bag trees'
+// leaves in tree order through the ballot mask of those lanes.
+__global__ void __launch_bounds__(256) rf_oob_predict(const uint64_t* __restrict__ X, int W, int64_t N,
+                                                      const int16_t* __restrict__ feat,
+                                                      const float* __restrict__ value, int T, int nodes,
+                                                      uint64_t seed, int t_off, float* __restrict__ out, int ldo,
+                                                      int32_t* __restrict__ count) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (r >= N) return;
+  float acc = 0.f;
+  int cnt = 0;
+  for (int t0 = 0; t0 < T; t0 += 64) {
+    const int t = t0 + lane;
+    int nd = 0;
+    const bool oob = t < T && rf_is_oob(rf_oob_key(seed, t + t_off), r);
+    if (oob) {
+      const int16_t* ft = feat + (int64_t)t * nodes;
+      int f = ft[0];
+      while (f >= 0) {
+        nd = 2 * nd + 1 + xbit(X, W, r, f);
+        f = ft[nd];
+      }
+    }
+    const uint64_t m = __ballot(oob);
+    cnt += __popcll(m);
+    const float* vb = value + (int64_t)t0 * nodes * 64 + lane;
+    for (uint64_t mm = m; mm; mm &= mm - 1) {  // (wave-uniform: ascending tree order)
+      const int k = (int)__builtin_ctzll(mm);
+      const int ndk = __shfl(nd, k);
+      acc += vb[((int64_t)k * nodes + ndk) * 64];
+    }
+  }
+  out[r * ldo + lane] = (lane < 62 && cnt > 0) ? acc / (float)cnt : 0.f;
+  if (lane == 0) count[r] = cnt;
+}
+
+// Tree-streamed form (W == 1, max_depth <= 8), on rf_predict_prepare's tree images: rf_predict_lds with a
+// per-lane out-of-bag test in front of every tree.  The tree's key is wave-uniform, so a lane pays one
+// mix64 per (row, tree); in-bag lanes skip the walk and the leaf reads, the row's count is a register,
+// and every output still adds its trees in ascending order: bit-identical to rf_oob_predict, no atomics.
+template <int G>
+__global__ void __launch_bounds__(RFP_WAVES * 64) rf_oob_predict_lds(const uint64_t* __restrict__ X, int64_t N,
+                                                          const uint8_t* __restrict__ prep, int T, int rows_per_wave,
+                                                          int64_t rows_per_block, uint64_t seed, int t_off,
+                                                          float* __restrict__ out, int ldo,
+                                                          int32_t* __restrict__ count) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t rw0 = (int64_t)blockIdx.x * rows_per_block + (int64_t)wave * rows_per_wave;
+  const int64_t rend = rw0 + rows_per_wave < N ? rw0 + rows_per_wave : N;
+  uint32_t xlo[G], xhi[G];
+  int cnt[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int64_t r = rw0 + 64 * g + lane;
+    const uint64_t x = r < rend ? X[r] : 0ull;
+    xlo[g] = (uint32_t)x;
+    xhi[g] = (uint32_t)(x >> 32);
+    cnt[g] = 0;
+  }
+  f32x4 acc[G][16];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int c = 0; c < 16; ++c) acc[g][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc((void*)prep, 0, 0x7FFFFFFF, 0x00020000);
+  auto stage = [&](int t) {  // (as rf_predict_lds)
+    char* dst = smem + (t & 1) * RFP_TREE;
+    for (int pc = wave; pc < RFP_TREE / 1024; pc += RFP_WAVES)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (EM_LDS void*)(dst + pc * 1024), 16, (uint32_t)lane * 16,
+                                               (uint32_t)t * RFP_TREE + (uint32_t)pc * 1024, 0, 0);
+  };
+  if (T > 0) stage(0);
+  const uint32_t rot = (uint32_t)lane << 4;
+  for (int t = 0; t < T; ++t) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of tree t have landed
+    __syncthreads();                                   // every wave's; and tree t - 1's buffer is free
+    if (t + 1 < T) stage(t + 1);
+    const char* buf = smem + (t & 1) * RFP_TREE;
+    const int16_t* enc = reinterpret_cast<const int16_t*>(buf);
+    const uint64_t key = rf_oob_key(seed, t + t_off);
+    bool oob[G];
+    int nd[G], f[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int64_t r = rw0 + 64 * g + lane;
+      oob[g] = r < rend && rf_is_oob(key, r);
+      cnt[g] += oob[g] ? 1 : 0;
+      nd[g] = 0;
+      f[g] = oob[g] ? (int)enc[0] : -1;  // in-bag lanes (and rows past the wave's) stay out of the walk
+    }
+    for (;;) {
+      bool more = false;
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        if (f[g] >= 0) {
+          const uint32_t w = f[g] < 32 ? xlo[g] : xhi[g];
+          nd[g] = 2 * nd[g] + 1 + (int)((w >> (f[g] & 31)) & 1u);
+          f[g] = enc[nd[g]];
+          more |= f[g] >= 0;
+        }
+      if (!__builtin_amdgcn_ballot_w64(more)) break;
+    }
+    // leaf chunks in rf_predict_lds's rotated order, for the out-of-bag lanes only (an in-bag lane's
+    // f = -1 would address leaf slot 0: inside the buffer, but it is never read)
+    uint32_t A[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) A[g] = 1024u + (uint32_t)(-f[g] - 1) * 256u + (rot & 0xF0u);
+#pragma unroll
+    for (int c0 = 0; c0 < 16; c0 += 4) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (oob[g]) {
+#pragma unroll
+          for (int c = c0; c < c0 + 4; ++c) {
+            const uint32_t base = ((lane & 15) + c >= 16) ? A[g] - 256u : A[g];
+            acc[g][c] += *reinterpret_cast<const f32x4*>(buf + base + 16u * c);
+          }
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        asm volatile("" : "+v"(acc[g][c0]), "+v"(acc[g][c0 + 1]), "+v"(acc[g][c0 + 2]), "+v"(acc[g][c0 + 3]));
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int64_t r = rw0 + 64 * g + lane;
+    if (r >= rend) continue;
+    const float cf = (float)cnt[g];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const int k = (lane + c) & 15;  // output chunk held in register set c
+      f32x4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (4 * k + e < 62 && cnt[g] > 0) ? acc[g][c][e] / cf : 0.f;
+      *reinterpret_cast<f32x4*>(out + r * ldo + 4 * k) = v;
+    }
+    count[r] = cnt[g];
+  }
+}
+
+// OOB metrics: one workgroup per 256 rows, one thread per row, over the rows with count > 0.  The
+// block's probabilities are staged into LDS (coalesced; row stride 63 words: a thread's row scan hits
+// its own bank), then per row the structured pick (topk_mask: the earlier index wins a tie), its hits
+// against the target mask, and the fp32 Brier sum and 62-term mean BCE (logf on the probability
+// clamped to [1e-7f, 1 - 1e-7f]).  Per block RFO_WORDS 64-bit words in a fixed order -- rows_used,
+// hits_main, hits_star, exact, mismatching pick bits, popcount(y), min count, sum count (int64), then the
+// fp64 sums of the per-row Brier and log-loss -- reduced by wave shuffles and over the 4 waves in wave
+// order: no atomics, the same bits every run.  The host adds the blocks in block order.
+constexpr int RFO_ROWS = 256, RFO_LD = 63, RFO_WORDS = 10;
+__global__ void __launch_bounds__(RFO_ROWS) rf_oob_metrics(const float* __restrict__ proba, int ldo,
+                                                           const int32_t* __restrict__ count,
+                                                           const uint64_t* __restrict__ Y, int64_t N,
+                                                           int64_t* __restrict__ partials) {
+  __shared__ float zs[RFO_ROWS * RFO_LD];
+  __shared__ int64_t wred[RFO_ROWS / 64][RFO_WORDS];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t r0 = (int64_t)blockIdx.x * RFO_ROWS;
+  const int nr = (int)(N - r0 < RFO_ROWS ? N - r0 : RFO_ROWS);
+  for (int i = tid; i < nr * 64; i += RFO_ROWS) {
+    const int row = i >> 6, col = i & 63;
+    if (col < 62) zs[row * RFO_LD + col] = proba[(r0 + row) * ldo + col];
+  }
+  __syncthreads();
+  const int c = tid < nr ? count[r0 + tid] : 0;
+  int used = 0, hm = 0, hs = 0, ex = 0, mism = 0, popy = 0, cmin = 0x7FFFFFFF;
+  double brier = 0.0, logl = 0.0;
+  if (c > 0) {
+    const float* z = zs + tid * RFO_LD;
+    const uint64_t y = Y[r0 + tid] & RF_M62;
+    const uint64_t pick = topk_mask<5>(z, 0, 50) | topk_mask<2>(z, 50, 62);
+    used = 1;
+    hm = __popcll(pick & y & MAIN_BITS);
+    hs = __popcll(pick & y & STAR_BITS);
+    mism = __popcll(pick ^ y);
+    ex = mism == 0 ? 1 : 0;
+    popy = __popcll(y);
+    cmin = c;
+    float b = 0.f, l = 0.f;
+    for (int j = 0; j < 62; ++j) {
+      const float p = z[j];
+      const bool yj = (y >> j) & 1ull;
+      const float d = p - (yj ? 1.f : 0.f);
+      b += d * d;
+      const float pc = fminf(fmaxf(p, 1e-7f), 1.f - 1e-7f);
+      l += -logf(yj ? pc : 1.f - pc);
+    }
+    brier = (double)b;
+    logl = (double)(l / 62.f);
+  }
+  long long csum = c > 0 ? c : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    used += __shfl_xor(used, o);
+    hm += __shfl_xor(hm, o);
+    hs += __shfl_xor(hs, o);
+    ex += __shfl_xor(ex, o);
+    mism += __shfl_xor(mism, o);
+    popy += __shfl_xor(popy, o);
+    const int om = __shfl_xor(cmin, o);
+    cmin = om < cmin ? om : cmin;
+    csum += __shfl_xor(csum, o);
+  }
+  brier = wave_sum_d(brier);
+  logl = wave_sum_d(logl);
+  if (lane == 0) {
+    int64_t* w = wred[wv];
+    w[0] = used, w[1] = hm, w[2] = hs, w[3] = ex, w[4] = mism, w[5] = popy, w[6] = cmin, w[7] = csum;
+    w[8] = __builtin_bit_cast(int64_t, brier);
+    w[9] = __builtin_bit_cast(int64_t, logl);
+  }
+  __syncthreads();
+  if (tid < RFO_WORDS) {
+    int64_t v = wred[0][tid];
+    for (int q = 1; q < RFO_ROWS / 64; ++q) {
+      const int64_t u = wred[q][tid];
+      if (tid == 6) v = u < v ? u : v;
+      else if (tid >= 8) v = __builtin_bit_cast(int64_t, __builtin_bit_cast(double, v) + __builtin_bit_cast(double, u));
+      else v += u;
+    }
+    partials[(int64_t)blockIdx.x * RFO_WORDS + tid] = v;
+  }
+}
+
 }  // namespace
 
 EM_API int em_rf_nodes(int max_depth) { return (1 << (max_depth + 1)) - 1; }
@@ -1452,6 +1692,73 @@ EM_API int em_rf_predict(const uint64_t* X, int W, int64_t N, const int16_t* fea
   }
   hipLaunchKernelGGL(rf_predict, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, X, W, N, feat, value, T, nodes,
                      out_logit, out, ldo);
+  EM_CHECK_LAUNCH();
+  return 0;
+}
+
+// Out-of-bag prediction (K11-OOB): out [N][ldo] fp32 (outputs 62 / 63 = 0), count [N] int32.  X must be the
+// matrix the trees [t_off, t_off + T) were fitted on (the row index is the hash key).  prep as em_rf_predict:
+// em_rf_predict_scratch(W, T, max_depth) bytes for the tree-streamed form, or null for the general one.
+EM_API int em_rf_oob_predict(const uint64_t* X, int W, int64_t N, const int16_t* feat, const float* value, int T,
+                             int max_depth, uint64_t seed, int t_off, float* out, int ldo, int32_t* count,
+                             void* prep, hipStream_t stream) {
+  if (!X || !feat || !value || !out || !count || W < 1 || N < 0 || T < 0 || ldo < 64 || max_depth < 0 ||
+      max_depth > 14 || t_off < 0 || (int64_t)T + (int64_t)t_off > 0x7FFFFFFFll)
+    return EM_ERR_ARG;
+  if (N == 0) return 0;
+  const int nodes = (1 << (max_depth + 1)) - 1;
+  if (prep && em_rf_predict_scratch(W, T, max_depth) > 0 && ((uintptr_t)prep & 15) == 0 && (ldo & 3) == 0 &&
+      ((uintptr_t)out & 15) == 0) {
+    hipLaunchKernelGGL(rf_predict_prepare, dim3(T), dim3(RFP_PREP_THREADS), 0, stream, feat, value, nodes, max_depth, (uint8_t*)prep);
+    EM_CHECK_LAUNCH();
+    static int cus = 0;
+    if (!cus) {
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          cus <= 0)
+        cus = 256;
+      (void)hipFuncSetAttribute((const void*)rf_oob_predict_lds<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * RFP_TREE);
+      (void)hipFuncSetAttribute((const void*)rf_oob_predict_lds<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * RFP_TREE);
+    }
+    // em_rf_predict's shape: one workgroup per CU, rows spread evenly, at most 2 x 64 rows per wave
+    constexpr int NW = RFP_WAVES;
+    int64_t grid = (N + 64 * NW - 1) / (64 * NW);
+    if (grid > cus) grid = cus;
+    int64_t rpw = ((N + grid - 1) / grid + NW - 1) / NW;
+    if (rpw > 128) {
+      rpw = 128;
+      grid = (N + NW * rpw - 1) / (NW * rpw);
+    }
+    const int G = (int)((rpw + 63) / 64);
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), 2 * RFP_TREE, stream, X, N, (const uint8_t*)prep,
+                         T, (int)rpw, NW * rpw, seed, t_off, out, ldo, count);
+    };
+    if (G == 1) go(rf_oob_predict_lds<1>);
+    else go(rf_oob_predict_lds<2>);
+    EM_CHECK_LAUNCH();
+    return 0;
+  }
+  hipLaunchKernelGGL(rf_oob_predict, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, X, W, N, feat, value, T, nodes,
+                     seed, t_off, out, ldo, count);
+  EM_CHECK_LAUNCH();
+  return 0;
+}
+
+// 64-bit words of em_rf_oob_metrics' partials for N rows: [blocks of 256 rows][10] (-1: bad N)
+EM_API int64_t em_rf_oob_metrics_words(int64_t N) { return N < 0 ? -1 : (N + RFO_ROWS - 1) / RFO_ROWS * RFO_WORDS; }
+
+// Metrics of an out-of-bag prediction over the rows with count > 0: proba [N][ldo] fp32 (outputs 0..61),
+// count [N], Y [N] target masks.  partials: em_rf_oob_metrics_words(N) words, 10 per block of 256 rows:
+// int64 rows_used, hits_main, hits_star, exact, mismatching bits, popcount(y), min count (INT32_MAX: no
+// row), sum count, then fp64 sum of the rows' Brier scores and of their mean 62-term BCE.
+EM_API int em_rf_oob_metrics(const float* proba, int ldo, const int32_t* count, const uint64_t* Y, int64_t N,
+                             void* partials, hipStream_t stream) {
+  if (!proba || !count || !Y || !partials || ldo < 62 || N < 0 || (N + RFO_ROWS - 1) / RFO_ROWS > 0x7FFFFFFFll)
+    return EM_ERR_ARG;
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(rf_oob_metrics, dim3((unsigned)((N + RFO_ROWS - 1) / RFO_ROWS)), dim3(RFO_ROWS), 0, stream, proba,
+                     ldo, count, Y, N, (int64_t*)partials);
   EM_CHECK_LAUNCH();
   return 0;
 }

@@ -40,7 +40,7 @@ _FLAGS = {
     "--eval-metric": "gbdt.eval_metric", "--nround": "gbdt.nround", "--lambda": "gbdt.reg_lambda",
     "--min-child-weight": "gbdt.min_child_weight", "--num-class": "gbdt.num_class", "--target": "gbdt.target", "--max-bin": "gbdt.max_bin",
     "--trees": "rf.n_trees", "--rf-max-depth": "rf.max_depth", "--min-samples-leaf": "rf.min_samples_leaf",
-    "--feature-subset": "rf.feature_subset",
+    "--feature-subset": "rf.feature_subset", "--oob": "rf.oob",
     "--hidden": "mlp.hidden", "--activation": "mlp.activation", "--loss": "mlp.loss", "--lr": "mlp.lr",
     "--batch": "mlp.batch", "--accum": "mlp.accum", "--steps": "mlp.steps", "--epochs": "mlp.epochs", "--dtype": "mlp.dtype",
     "--weight-decay": "mlp.weight_decay", "--eval-every": "mlp.eval_every",

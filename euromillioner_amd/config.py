@@ -85,6 +85,7 @@ class RFConfig:
     bootstrap: bool = True
     seed: int = 0
     device: str = "auto"
+    oob: bool = False  # train: add the out-of-bag score and the top feature importances to the result
 
 
 @dataclasses.dataclass

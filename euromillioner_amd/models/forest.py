@@ -125,6 +125,8 @@ class RandomForest:
         self.F = None
         self.feat = self.value = self.gain = self.cover = None
         self.backend_used = None
+        self.n_train = None  # rows of the last fit (None: unknown, e.g. an older forest file)
+        self.tree_start = 0  # global id of tree 0 (fit with an explicit trees= range)
 
     # ------------------------------------------------------------------ fit
     def _backend(self) -> str:
@@ -149,6 +151,8 @@ class RandomForest:
             raise ValueError("F exceeds the packed feature words (max 256)")
         self.F = int(F)
         self.k = n_candidates(self.feature_subset, F)
+        self.n_train = len(X)
+        self.tree_start = int(trees.start) if trees is not None and group is None else 0
         if trees is None:
             trees = range(self.n_trees)
             if group is not None:
@@ -218,11 +222,54 @@ class RandomForest:
 
         return K.predict(X, self.feat, self.value, self.max_depth, out_logit=out_logit)
 
+    # ------------------------------------------------------------------ out-of-bag evaluation, importances
+    def _oob_device(self, X):
+        from ..ops import forest as K
+        from .forest_oob import check_oob_args
+
+        X = check_oob_args(self, X)
+        return K.oob_predict(X, self.feat, self.value, self.max_depth, self.seed, self.tree_start)
+
+    def oob_predict_proba(self, X: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """(proba [N, 62] float32, count [N] int32): per training row the mean leaf vector over the trees it
+        is out of bag for (bootstrap weight 0) and their number.  ``X`` must be the matrix of the fit, same
+        rows in the same order: the row index is the hash key.  Definitions: ``models/forest_oob.py``."""
+        from .forest_oob import oob_predict_proba_numpy
+
+        if self._backend() == "hip":
+            out, count = self._oob_device(X)
+            return out[:, :62].cpu().numpy(), count.cpu().numpy()
+        return oob_predict_proba_numpy(self, X)
+
+    def oob_score(self, X: np.ndarray, Y: np.ndarray) -> dict:
+        """The forest's out-of-bag score on its training rows (X as ``oob_predict_proba``, Y [N] target masks):
+        rows, rows_without_oob_tree, min_trees, mean_trees, hits_main, hits_star, exact, acc, trivial_acc,
+        brier, logloss over the rows with at least one out-of-bag tree."""
+        from .forest_oob import oob_finish, oob_predict_proba_numpy, oob_totals_numpy
+
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.uint64).reshape(-1))
+        if len(Y) != len(X):
+            raise ValueError("X and Y row counts differ")
+        if self._backend() == "hip":
+            from ..ops import forest as K
+
+            out, count = self._oob_device(X)
+            return K.oob_metrics(out, count, Y)
+        proba, count = oob_predict_proba_numpy(self, X)
+        return oob_finish(oob_totals_numpy(proba, count, Y))
+
+    def feature_importances(self, kind: str = "gain") -> np.ndarray:
+        """[F] float64 shares of the split nodes' gain | cover | splits per feature (sum 1; zeros without a split)."""
+        from .forest_oob import feature_importances
+
+        return feature_importances(self, kind)
+
     # ------------------------------------------------------------------ persistence (T6 tree file)
     def meta(self) -> dict:
         return {"format": "euromillioner-forest-v1", "n_trees": len(self.feat), "max_depth": self.max_depth,
                 "min_samples_leaf": self.min_samples_leaf, "feature_subset": str(self.feature_subset),
-                "bootstrap": self.bootstrap, "seed": self.seed, "F": self.F, "k": self.k}
+                "bootstrap": self.bootstrap, "seed": self.seed, "F": self.F, "k": self.k,
+                "n_train": self.n_train, "tree_start": self.tree_start}
 
     def save(self, path: str) -> None:
         """``.npz`` of plain arrays + JSON meta (loadable with allow_pickle=False)."""
@@ -238,5 +285,6 @@ class RandomForest:
         rf = cls(meta["n_trees"], meta["max_depth"], meta["min_samples_leaf"], meta["feature_subset"],
                  meta["bootstrap"], meta["seed"])
         rf.F, rf.k = meta["F"], meta["k"]
+        rf.n_train, rf.tree_start = meta.get("n_train"), int(meta.get("tree_start", 0))  # (absent in older files)
         rf.feat, rf.value, rf.gain, rf.cover = z["feat"], z["value"], z["gain"], z["cover"]
         return rf

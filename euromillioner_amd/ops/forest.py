@@ -1,5 +1,5 @@
 """Python face of the random-forest kernels (``csrc/forest.hip``: K8 hist, K9 split scan,
-K10 partition, K11 predict) and their native level-wise driver ``em_rf_fit``.
+K10 partition, K11 predict, K11-OOB out-of-bag predict and metrics) and their native level-wise driver ``em_rf_fit``.
 
 The reference only declares Spark MLlib's RandomForest (``/root/reference/pom.xml:56-61``,
 ``README.md:6``); SURVEY.md §2.4 N7 / BASELINE config 4 define the 100-tree one-hot forest."""
@@ -21,6 +21,11 @@ N.register_signatures({
     "em_rf_predict": (N._i32, [N._c_void_p, N._i32, N._i64, N._c_void_p, N._c_void_p, N._i32, N._i32, N._i32,
                                N._c_void_p, N._i32, N._c_void_p, N._c_void_p]),
     "em_rf_predict_scratch": (N._i64, [N._i32, N._i32, N._i32]),
+    "em_rf_oob_predict": (N._i32, [N._c_void_p, N._i32, N._i64, N._c_void_p, N._c_void_p, N._i32, N._i32,
+                                   N.ctypes.c_uint64, N._i32, N._c_void_p, N._i32, N._c_void_p, N._c_void_p,
+                                   N._c_void_p]),
+    "em_rf_oob_metrics_words": (N._i64, [N._i64]),
+    "em_rf_oob_metrics": (N._i32, [N._c_void_p, N._i32, N._c_void_p, N._c_void_p, N._i64, N._c_void_p, N._c_void_p]),
 })
 
 
@@ -88,3 +93,63 @@ def predict(X, feat, value, max_depth: int, out_logit: bool = False, device="cud
     N.call("em_rf_predict", Xd.data_ptr(), W, n, fd.data_ptr(), vd.data_ptr(), T, max_depth, int(out_logit),
            out.data_ptr(), 64, prep.data_ptr() if prep is not None else None, N.stream_handle(dev))
     return out
+
+
+def oob_predict(X, feat, value, max_depth: int, seed: int, t_off: int = 0, stream_trees: bool = True, device="cuda"
+                ) -> tuple[torch.Tensor, torch.Tensor]:
+    """K11-OOB: per row the mean leaf vector over the trees it is out of bag for -> (out [N, 64] fp32, count [N]
+    int32).  ``X`` must be the matrix trees ``t_off .. t_off + T - 1`` (global ids) were fitted on with ``seed``:
+    the in-bag sets are recomputed from the hash of (seed, tree id, row).  Rows without an out-of-bag tree are
+    all zero with count 0.  ``stream_trees`` as :func:`predict` (rf_oob_predict_lds, bit-identical)."""
+    dev = torch.device(device)
+    Xd = X if isinstance(X, torch.Tensor) else _u64_to_device(X, dev)
+    n = Xd.shape[0]
+    W = Xd.shape[1] if Xd.dim() == 2 else 1
+    fd = feat if isinstance(feat, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feat)).to(dev)
+    vd = value if isinstance(value, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(value)).to(dev)
+    T = fd.shape[0]
+    if fd.shape[1] != (1 << (max_depth + 1)) - 1:
+        raise ValueError("feat does not match max_depth")
+    out = torch.empty(n, 64, dtype=torch.float32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    nb = N.lib().em_rf_predict_scratch(W, T, max_depth) if stream_trees else 0
+    prep = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev) if nb > 0 else None
+    N.call("em_rf_oob_predict", Xd.data_ptr(), W, n, fd.data_ptr(), vd.data_ptr(), T, max_depth,
+           int(seed) & 0xFFFFFFFFFFFFFFFF, int(t_off), out.data_ptr(), 64, count.data_ptr(),
+           prep.data_ptr() if prep is not None else None, N.stream_handle(dev))
+    return out, count
+
+
+def oob_totals(out: torch.Tensor, count: torch.Tensor, Y) -> dict:
+    """em_rf_oob_metrics: the per-block partials of the rows with count > 0, added on the host in block order
+    (integers exactly, the fp64 Brier / log-loss sums one block after the other).  Keys as
+    ``models.forest_oob.oob_totals_numpy``."""
+    from ..models.forest_oob import TOTAL_KEYS
+
+    N.check_cuda(out, "out", torch.float32)
+    N.check_cuda(count, "count", torch.int32)
+    n = out.shape[0]
+    if out.dim() != 2 or out.shape[1] < 62 or count.numel() != n:
+        raise ValueError("out must be [N, >= 62] and count [N]")
+    Yd = Y if isinstance(Y, torch.Tensor) else _u64_to_device(np.asarray(Y).reshape(-1), out.device)
+    if Yd.numel() != n:
+        raise ValueError("Y and out row counts differ")
+    words = N.query("em_rf_oob_metrics_words", n)
+    part = torch.empty(max(words, 1), dtype=torch.int64, device=out.device)
+    N.call("em_rf_oob_metrics", out.data_ptr(), out.stride(0), count.data_ptr(), Yd.data_ptr(), n, part.data_ptr(),
+           N.stream_handle(out.device))
+    p = part[:words].cpu().numpy().reshape(-1, 10)
+    tot = {k: int(p[:, i].sum()) for i, k in enumerate(TOTAL_KEYS[:8]) if k != "min_trees"}
+    tot["min_trees"] = int(p[:, 6].min()) if len(p) and tot["rows"] > 0 else 0
+    fl = p[:, 8:].copy().view(np.float64)
+    tot["brier_sum"] = float(np.cumsum(fl[:, 0])[-1]) if len(p) else 0.0  # (cumsum: strictly in block order)
+    tot["logloss_sum"] = float(np.cumsum(fl[:, 1])[-1]) if len(p) else 0.0
+    tot["n"] = int(n)
+    return tot
+
+
+def oob_metrics(out: torch.Tensor, count: torch.Tensor, Y) -> dict:
+    """The out-of-bag score of (out, count) = :func:`oob_predict` against the target masks ``Y`` [N]."""
+    from ..models.forest_oob import oob_finish
+
+    return oob_finish(oob_totals(out, count, Y))

@@ -587,6 +587,10 @@ def train_rf(cfg: RunConfig) -> dict:
             z = torch.logit(torch.from_numpy(p).double().clamp(1e-7, 1 - 1e-7)).float()
             yt = torch.from_numpy(multi_hot(ds.numbers[margin + cfg.data.lags:]))
             res["val"] = draw_metrics_torch(z, yt[:len(z)], "bce")
+        if r.oob:  # (after the gather: every rank holds all the trees, rank 0's result is the forest's)
+            res["oob"] = rf.oob_score(X[:margin], Y[:margin])
+            imp = rf.feature_importances("gain")
+            res["importances_top"] = [[int(f), float(imp[f])] for f in np.argsort(-imp, kind="stable")[:5]]
         if cfg.ckpt.path and info.rank == 0:
             rf.save(cfg.ckpt.path)
             res["checkpoint"] = cfg.ckpt.path
