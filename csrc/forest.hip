@@ -1005,17 +1005,53 @@ __global__ void __launch_bounds__(RF_NT) rf_partition(RfParams p, const void* __
 // NOTE (ROCm 7.2): holding the row's feature words in registers and picking one with a per-lane
 // select chain + 64-bit shift produced wrong bits for ~3 % of rows on gfx950; reading the bit
 // through xbit() (an L1-resident load) is exact -- tests/test_forest.py checks the deep-tree case.
+//
+// K11-OOB (OOB = true): out-of-bag prediction.  Row i is out of bag for tree t when its bootstrap weight is
+// 0, and the weight is a pure function of (seed, global tree id, row): row_weight() == 0 <=> poisson1's
+// m < th[0], so the in-bag sets are recomputed here from the hash and nothing of the fit is stored.  Per
+// row: the sum of the leaf vectors of its out-of-bag trees (fp32, ascending tree order) over their count;
+// rows without an out-of-bag tree get zeros and count 0.  Outputs 62 / 63 are 0.  Both predict kernels take
+// OOB as a template flag: a lane hashes in front of every tree and -- only when its row is out of bag --
+// walks it and adds its leaf; the plain instantiations carry none of it.
+constexpr uint64_t RF_OOB_TH0 = 0xbc5ab1b16779cull;  // poisson1's th[0] = cdf(0) * 2^53
+// hash3(seed, 2^32 + tree, row) = mix64(key ^ row) with the tree's key = mix64(seed ^ mix64(2^32 + tree))
+EM_DEVICE uint64_t rf_oob_key(uint64_t seed, int tree) { return mix64(seed ^ mix64(0x100000000ull + (uint64_t)tree)); }
+EM_DEVICE bool rf_is_oob(uint64_t key, int64_t row) { return (mix64(key ^ (uint64_t)row) >> 11) < RF_OOB_TH0; }
+
+// output o of a row from its sum over `div` trees: all T (plain: probability or logit), or the row's
+// out-of-bag count
+template <bool OOB>
+EM_DEVICE float rf_mean_out(float acc, int o, int div, int out_logit) {
+  if constexpr (OOB) return (o < 62 && div > 0) ? acc / (float)div : 0.f;
+  float pr = div > 0 ? acc / (float)div : 0.f;
+  if (out_logit) {
+    const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
+    pr = o < 62 ? __logf(pc / (1.f - pc)) : -30.f;
+  } else if (o >= 62) {
+    pr = 0.f;
+  }
+  return pr;
+}
+
+// General form (any W, any depth).  The gather takes the lanes that walked, lowest first (ascending tree
+// order): all t < T, or with OOB the ballot mask of the out-of-bag ones.  seed, t_off and count are read
+// only when OOB.
+template <bool OOB>
 __global__ void __launch_bounds__(256) rf_predict(const uint64_t* __restrict__ X, int W, int64_t N,
                                                   const int16_t* __restrict__ feat, const float* __restrict__ value,
-                                                  int T, int nodes, int out_logit, float* __restrict__ out, int ldo) {
+                                                  int T, int nodes, int out_logit, uint64_t seed, int t_off,
+                                                  float* __restrict__ out, int ldo, int32_t* __restrict__ count) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (r >= N) return;
   float acc = 0.f;
+  int cnt = 0;
   for (int t0 = 0; t0 < T; t0 += 64) {
     const int t = t0 + lane;
     int nd = 0;
-    if (t < T) {
+    bool in = t < T;
+    if constexpr (OOB) in = in && rf_is_oob(rf_oob_key(seed, t + t_off), r);
+    if (in) {
       const int16_t* ft = feat + (int64_t)t * nodes;
       int f = ft[0];
       while (f >= 0) {
@@ -1023,21 +1059,20 @@ __global__ void __launch_bounds__(256) rf_predict(const uint64_t* __restrict__ X
         f = ft[nd];
       }
     }
-    const int cnt = T - t0 < 64 ? T - t0 : 64;
     const float* vb = value + (int64_t)t0 * nodes * 64 + lane;
-    for (int k = 0; k < cnt; ++k) {
-      const int ndk = __shfl(nd, k);
-      acc += vb[((int64_t)k * nodes + ndk) * 64];
+    auto add = [&](int k) { acc += vb[((int64_t)k * nodes + __shfl(nd, k)) * 64]; };
+    if constexpr (OOB) {
+      const uint64_t m = __ballot(in);
+      cnt += __popcll(m);
+      for (uint64_t mm = m; mm; mm &= mm - 1) add((int)__builtin_ctzll(mm));  // (wave-uniform)
+    } else {  // the mask would be lanes 0 .. live - 1: counted, the loop is two instructions shorter (0.3 % measured)
+      const int live = T - t0 < 64 ? T - t0 : 64;
+      for (int k = 0; k < live; ++k) add(k);
     }
   }
-  float pr = T > 0 ? acc / (float)T : 0.f;
-  if (out_logit) {
-    const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
-    pr = lane < 62 ? __logf(pc / (1.f - pc)) : -30.f;
-  } else if (lane >= 62) {
-    pr = 0.f;
-  }
-  out[r * ldo + lane] = pr;
+  out[r * ldo + lane] = rf_mean_out<OOB>(acc, lane, OOB ? cnt : T, out_logit);
+  if constexpr (OOB)
+    if (lane == 0) count[r] = cnt;
 }
 
 // K11, tree-streamed form (W == 1, max_depth <= 8: at most 256 leaves per tree).  Predict was bound by
@@ -1050,7 +1085,9 @@ __global__ void __launch_bounds__(256) rf_predict(const uint64_t* __restrict__ X
 // order is rotated by the lane (step c reads chunk (lane + c) & 15), so the 16 lanes of a ds_read_b128
 // phase always hit 16 different bank groups whatever leaves they read, and register set c of lane l
 // holds output chunk (l + c) & 15 (un-rotated by the store addresses).  Every output still sums its
-// trees in tree order, so the result is bit-identical to rf_predict.
+// trees in tree order, so the result is bit-identical to rf_predict.  With OOB the tree's key is
+// wave-uniform, so a lane pays one mix64 per (row, tree); in-bag lanes skip the walk and the leaf reads
+// and the row's count is a register: bit-identical to rf_predict<true>, no atomics.
 constexpr int RFP_TREE = 1024 + 256 * 256;  // bytes per prepared tree: node table + 256 leaf vectors
 
 // one workgroup per tree: node table with leaves encoded, leaf vectors compacted in level order;
@@ -1120,25 +1157,28 @@ __global__ void __launch_bounds__(RFP_PREP_THREADS) rf_predict_prepare(const int
 // RFP_WAVES waves per workgroup, at most 2 x 64 rows per wave: 3 waves per SIMD hide the walk's
 // dependent LDS reads, and 64 accumulators per row fit the 168 VGPRs a wave gets (a 3-group form at
 // 2 waves per SIMD needed 192 accumulators and spilled 576 B per lane to scratch: 2.27 ms for 300 k
-// rows x 100 trees, round 5)
+// rows x 100 trees, round 5).  out_logit is read only by the plain kernel; seed, t_off and count only when OOB.
 constexpr int RFP_WAVES = 12;
-template <int G>
+template <int G, bool OOB>
 __global__ void __launch_bounds__(RFP_WAVES * 64) rf_predict_lds(const uint64_t* __restrict__ X, int64_t N,
                                                       const uint8_t* __restrict__ prep, int T, int rows_per_wave,
-                                                      int64_t rows_per_block, int out_logit, float* __restrict__ out,
-                                                      int ldo) {
+                                                      int64_t rows_per_block, int out_logit, uint64_t seed, int t_off,
+                                                      float* __restrict__ out, int ldo,
+                                                      int32_t* __restrict__ count) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t rw0 = (int64_t)blockIdx.x * rows_per_block + (int64_t)wave * rows_per_wave;
   const int64_t rend = rw0 + rows_per_wave < N ? rw0 + rows_per_wave : N;
   uint32_t xlo[G], xhi[G];
+  [[maybe_unused]] int cnt[G];  // (OOB) trees the lane's row is out of bag for
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int64_t r = rw0 + 64 * g + lane;
     const uint64_t x = r < rend ? X[r] : 0ull;
     xlo[g] = (uint32_t)x;
     xhi[g] = (uint32_t)(x >> 32);
+    cnt[g] = 0;
   }
   f32x4 acc[G][16];
 #pragma unroll
@@ -1165,12 +1205,23 @@ __global__ void __launch_bounds__(RFP_WAVES * 64) rf_predict_lds(const uint64_t*
     const char* buf = smem + (t & 1) * RFP_TREE;
     const int16_t* enc = reinterpret_cast<const int16_t*>(buf);
     // the G row groups walk the tree together: their dependent node reads are independent of each
-    // other, so each step has G reads in flight instead of one
+    // other, so each step has G reads in flight instead of one.  in[g]: the lane takes part in tree t --
+    // plain: wave-uniform, groups past the wave's rows stay out; OOB: per lane, its row is out of bag
+    [[maybe_unused]] uint64_t key = 0;
+    if constexpr (OOB) key = rf_oob_key(seed, t + t_off);
+    bool in[G];
     int nd[G], f[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
+      if constexpr (OOB) {
+        const int64_t r = rw0 + 64 * g + lane;
+        in[g] = r < rend && rf_is_oob(key, r);
+        cnt[g] += in[g] ? 1 : 0;
+      } else {
+        in[g] = rw0 + 64 * g < rend;
+      }
       nd[g] = 0;
-      f[g] = rw0 + 64 * g < rend ? (int)enc[0] : -1;  // (wave-uniform: groups past the wave's rows stay out)
+      f[g] = in[g] ? (int)enc[0] : -1;
     }
     for (;;) {
       bool more = false;
@@ -1187,7 +1238,8 @@ __global__ void __launch_bounds__(RFP_WAVES * 64) rf_predict_lds(const uint64_t*
     // leaf chunks: lane l reads chunk (l + c) & 15 at step c from base A = leaf + ((l & 15) << 4), or
     // A - 256 once the rotation wraps: one select per step and the step's 16 c in the instruction's
     // immediate offset.  4 steps at a time for every group together (the groups' reads in flight at
-    // once), each batch's adds done before the next batch's reads issue (register budget).
+    // once), each batch's adds done before the next batch's reads issue (register budget).  A lane that
+    // stayed out has f = -1, which would address leaf slot 0: inside the buffer, but it is never read.
     uint32_t A[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) A[g] = 1024u + (uint32_t)(-f[g] - 1) * 256u + (rot & 0xF0u);
@@ -1195,7 +1247,10 @@ __global__ void __launch_bounds__(RFP_WAVES * 64) rf_predict_lds(const uint64_t*
     for (int c0 = 0; c0 < 16; c0 += 4) {
 #pragma unroll
       for (int g = 0; g < G; ++g) {
-        if (rw0 + 64 * g >= rend) break;  // (wave-uniform)
+        if (!in[g]) {
+          if constexpr (OOB) continue;
+          else break;  // (wave-uniform, and so are the groups after it)
+        }
 #pragma unroll
         for (int c = c0; c < c0 + 4; ++c) {
           const uint32_t base = ((lane & 15) + c >= 16) ? A[g] - 256u : A[g];
@@ -1207,8 +1262,6 @@ __global__ void __launch_bounds__(RFP_WAVES * 64) rf_predict_lds(const uint64_t*
         asm volatile("" : "+v"(acc[g][c0]), "+v"(acc[g][c0 + 1]), "+v"(acc[g][c0 + 2]), "+v"(acc[g][c0 + 3]));
     }
   }
-  const float invT = 1.f / (float)(T > 0 ? T : 1);
-  (void)invT;
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int64_t r = rw0 + 64 * g + lane;
@@ -1218,175 +1271,10 @@ __global__ void __launch_bounds__(RFP_WAVES * 64) rf_predict_lds(const uint64_t*
       const int k = (lane + c) & 15;  // output chunk held in register set c
       f32x4 v;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int o = 4 * k + e;
-        float pr = T > 0 ? acc[g][c][e] / (float)T : 0.f;
-        if (out_logit) {
-          const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
-          pr = o < 62 ? __logf(pc / (1.f - pc)) : -30.f;
-        } else if (o >= 62) {
-          pr = 0.f;
-        }
-        v[e] = pr;
-      }
+      for (int e = 0; e < 4; ++e) v[e] = rf_mean_out<OOB>(acc[g][c][e], 4 * k + e, OOB ? cnt[g] : T, out_logit);
       *reinterpret_cast<f32x4*>(out + r * ldo + 4 * k) = v;
     }
-  }
-}
-
-// K11-OOB: out-of-bag prediction.  Row i is out of bag for tree t when its bootstrap weight is 0, and the
-// weight is a pure function of (seed, global tree id, row): row_weight() == 0 <=> poisson1's m < th[0], so
-// the in-bag sets are recomputed here from the hash and nothing of the fit is stored.  Per row: the sum of
-// the leaf vectors of its out-of-bag trees (fp32, ascending tree order) over their count; rows without an
-// out-of-bag tree get zeros and count 0.  Outputs 62 / 63 are 0.  Two bit-identical forms, as K11.
-constexpr uint64_t RF_OOB_TH0 = 0xbc5ab1b16779cull;  // poisson1's th[0] = cdf(0) * 2^53
-// hash3(seed, 2^32 + tree, row) = mix64(key ^ row) with the tree's key = mix64(seed ^ mix64(2^32 + tree))
-EM_DEVICE uint64_t rf_oob_key(uint64_t seed, int tree) { return mix64(seed ^ mix64(0x100000000ull + (uint64_t)tree)); }
-EM_DEVICE bool rf_is_oob(uint64_t key, int64_t row) { return (mix64(key ^ (uint64_t)row) >> 11) < RF_OOB_TH0; }
-
-// General form (any W, any depth): one wavefront per row as rf_predict; lane l hashes and -- only when the
-// row is out of bag for it -- walks tree t0 + l, then lane j (= output j) gathers the out-of-bag trees'
-// leaves in tree order through the ballot mask of those lanes.
-__global__ void __launch_bounds__(256) rf_oob_predict(const uint64_t* __restrict__ X, int W, int64_t N,
-                                                      const int16_t* __restrict__ feat,
-                                                      const float* __restrict__ value, int T, int nodes,
-                                                      uint64_t seed, int t_off, float* __restrict__ out, int ldo,
-                                                      int32_t* __restrict__ count) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (r >= N) return;
-  float acc = 0.f;
-  int cnt = 0;
-  for (int t0 = 0; t0 < T; t0 += 64) {
-    const int t = t0 + lane;
-    int nd = 0;
-    const bool oob = t < T && rf_is_oob(rf_oob_key(seed, t + t_off), r);
-    if (oob) {
-      const int16_t* ft = feat + (int64_t)t * nodes;
-      int f = ft[0];
-      while (f >= 0) {
-        nd = 2 * nd + 1 + xbit(X, W, r, f);
-        f = ft[nd];
-      }
-    }
-    const uint64_t m = __ballot(oob);
-    cnt += __popcll(m);
-    const float* vb = value + (int64_t)t0 * nodes * 64 + lane;
-    for (uint64_t mm = m; mm; mm &= mm - 1) {  // (wave-uniform: ascending tree order)
-      const int k = (int)__builtin_ctzll(mm);
-      const int ndk = __shfl(nd, k);
-      acc += vb[((int64_t)k * nodes + ndk) * 64];
-    }
-  }
-  out[r * ldo + lane] = (lane < 62 && cnt > 0) ? acc / (float)cnt : 0.f;
-  if (lane == 0) count[r] = cnt;
-}
-
-// Tree-streamed form (W == 1, max_depth <= 8), on rf_predict_prepare's tree images: rf_predict_lds with a
-// per-lane out-of-bag test in front of every tree.  The tree's key is wave-uniform, so a lane pays one
-// mix64 per (row, tree); in-bag lanes skip the walk and the leaf reads, the row's count is a register,
-// and every output still adds its trees in ascending order: bit-identical to rf_oob_predict, no atomics.
-template <int G>
-__global__ void __launch_bounds__(RFP_WAVES * 64) rf_oob_predict_lds(const uint64_t* __restrict__ X, int64_t N,
-                                                          const uint8_t* __restrict__ prep, int T, int rows_per_wave,
-                                                          int64_t rows_per_block, uint64_t seed, int t_off,
-                                                          float* __restrict__ out, int ldo,
-                                                          int32_t* __restrict__ count) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t rw0 = (int64_t)blockIdx.x * rows_per_block + (int64_t)wave * rows_per_wave;
-  const int64_t rend = rw0 + rows_per_wave < N ? rw0 + rows_per_wave : N;
-  uint32_t xlo[G], xhi[G];
-  int cnt[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const int64_t r = rw0 + 64 * g + lane;
-    const uint64_t x = r < rend ? X[r] : 0ull;
-    xlo[g] = (uint32_t)x;
-    xhi[g] = (uint32_t)(x >> 32);
-    cnt[g] = 0;
-  }
-  f32x4 acc[G][16];
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int c = 0; c < 16; ++c) acc[g][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)prep, 0, 0x7FFFFFFF, 0x00020000);
-  auto stage = [&](int t) {  // (as rf_predict_lds)
-    char* dst = smem + (t & 1) * RFP_TREE;
-    for (int pc = wave; pc < RFP_TREE / 1024; pc += RFP_WAVES)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (EM_LDS void*)(dst + pc * 1024), 16, (uint32_t)lane * 16,
-                                               (uint32_t)t * RFP_TREE + (uint32_t)pc * 1024, 0, 0);
-  };
-  if (T > 0) stage(0);
-  const uint32_t rot = (uint32_t)lane << 4;
-  for (int t = 0; t < T; ++t) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of tree t have landed
-    __syncthreads();                                   // every wave's; and tree t - 1's buffer is free
-    if (t + 1 < T) stage(t + 1);
-    const char* buf = smem + (t & 1) * RFP_TREE;
-    const int16_t* enc = reinterpret_cast<const int16_t*>(buf);
-    const uint64_t key = rf_oob_key(seed, t + t_off);
-    bool oob[G];
-    int nd[G], f[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const int64_t r = rw0 + 64 * g + lane;
-      oob[g] = r < rend && rf_is_oob(key, r);
-      cnt[g] += oob[g] ? 1 : 0;
-      nd[g] = 0;
-      f[g] = oob[g] ? (int)enc[0] : -1;  // in-bag lanes (and rows past the wave's) stay out of the walk
-    }
-    for (;;) {
-      bool more = false;
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-        if (f[g] >= 0) {
-          const uint32_t w = f[g] < 32 ? xlo[g] : xhi[g];
-          nd[g] = 2 * nd[g] + 1 + (int)((w >> (f[g] & 31)) & 1u);
-          f[g] = enc[nd[g]];
-          more |= f[g] >= 0;
-        }
-      if (!__builtin_amdgcn_ballot_w64(more)) break;
-    }
-    // leaf chunks in rf_predict_lds's rotated order, for the out-of-bag lanes only (an in-bag lane's
-    // f = -1 would address leaf slot 0: inside the buffer, but it is never read)
-    uint32_t A[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) A[g] = 1024u + (uint32_t)(-f[g] - 1) * 256u + (rot & 0xF0u);
-#pragma unroll
-    for (int c0 = 0; c0 < 16; c0 += 4) {
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        if (oob[g]) {
-#pragma unroll
-          for (int c = c0; c < c0 + 4; ++c) {
-            const uint32_t base = ((lane & 15) + c >= 16) ? A[g] - 256u : A[g];
-            acc[g][c] += *reinterpret_cast<const f32x4*>(buf + base + 16u * c);
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-        asm volatile("" : "+v"(acc[g][c0]), "+v"(acc[g][c0 + 1]), "+v"(acc[g][c0 + 2]), "+v"(acc[g][c0 + 3]));
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const int64_t r = rw0 + 64 * g + lane;
-    if (r >= rend) continue;
-    const float cf = (float)cnt[g];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-      const int k = (lane + c) & 15;  // output chunk held in register set c
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (4 * k + e < 62 && cnt[g] > 0) ? acc[g][c][e] / cf : 0.f;
-      *reinterpret_cast<f32x4*>(out + r * ldo + 4 * k) = v;
-    }
-    count[r] = cnt[g];
+    if constexpr (OOB) count[r] = cnt[g];
   }
 }
 
@@ -1651,47 +1539,57 @@ EM_API int64_t em_rf_predict_scratch(int W, int T, int max_depth) {
   return (int64_t)T * RFP_TREE;
 }
 
+// The tree-streamed launch of em_rf_predict (oob = false) and em_rf_oob_predict, arguments as theirs.
+// Returns RF_NOT_STREAMED, with nothing launched, when that form does not apply (no prep, forest shape,
+// alignment); else 0 or the launch's error.
+constexpr int RF_NOT_STREAMED = -2;
+static int rf_predict_streamed(bool oob, const uint64_t* X, int W, int64_t N, const int16_t* feat, const float* value,
+                               int T, int max_depth, int out_logit, uint64_t seed, int t_off, float* out, int ldo,
+                               int32_t* count, void* prep, hipStream_t stream) {
+  if (!prep || em_rf_predict_scratch(W, T, max_depth) <= 0 || ((uintptr_t)prep & 15) != 0 || (ldo & 3) != 0 ||
+      ((uintptr_t)out & 15) != 0)
+    return RF_NOT_STREAMED;
+  hipLaunchKernelGGL(rf_predict_prepare, dim3(T), dim3(RFP_PREP_THREADS), 0, stream, feat, value,
+                     (1 << (max_depth + 1)) - 1, max_depth, (uint8_t*)prep);
+  EM_CHECK_LAUNCH();
+  using Kern = decltype(&rf_predict_lds<1, false>);
+  static const Kern kerns[4] = {rf_predict_lds<1, false>, rf_predict_lds<2, false>, rf_predict_lds<1, true>,
+                                rf_predict_lds<2, true>};  // [2 * oob + G - 1]
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+      cus = 256;
+    for (const Kern k : kerns)
+      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * RFP_TREE);
+  }
+  // one workgroup per CU (the LDS double buffer), rows spread evenly; at most 2 x 64 rows per wave
+  constexpr int NW = RFP_WAVES;
+  int64_t grid = (N + 64 * NW - 1) / (64 * NW);
+  if (grid > cus) grid = cus;
+  int64_t rpw = ((N + grid - 1) / grid + NW - 1) / NW;
+  if (rpw > 128) {
+    rpw = 128;
+    grid = (N + NW * rpw - 1) / (NW * rpw);
+  }
+  const int G = (int)((rpw + 63) / 64);
+  hipLaunchKernelGGL(kerns[2 * oob + G - 1], dim3((unsigned)grid), dim3(NW * 64), 2 * RFP_TREE, stream, X, N,
+                     (const uint8_t*)prep, T, (int)rpw, NW * rpw, out_logit, seed, t_off, out, ldo, count);
+  EM_CHECK_LAUNCH();
+  return 0;
+}
+
 // prep: em_rf_predict_scratch(W, T, max_depth) bytes (16-B aligned), or null for the one-wave-per-row path
 EM_API int em_rf_predict(const uint64_t* X, int W, int64_t N, const int16_t* feat, const float* value, int T,
                          int max_depth, int out_logit, float* out, int ldo, void* prep, hipStream_t stream) {
   if (!X || !feat || !value || !out || W < 1 || N < 0 || T < 0 || ldo < 64 || max_depth < 0 || max_depth > 14)
     return EM_ERR_ARG;
   if (N == 0) return 0;
-  const int nodes = (1 << (max_depth + 1)) - 1;
-  if (prep && em_rf_predict_scratch(W, T, max_depth) > 0 && ((uintptr_t)prep & 15) == 0 && (ldo & 3) == 0 &&
-      ((uintptr_t)out & 15) == 0) {
-    hipLaunchKernelGGL(rf_predict_prepare, dim3(T), dim3(RFP_PREP_THREADS), 0, stream, feat, value, nodes, max_depth, (uint8_t*)prep);
-    EM_CHECK_LAUNCH();
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          cus <= 0)
-        cus = 256;
-      (void)hipFuncSetAttribute((const void*)rf_predict_lds<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * RFP_TREE);
-      (void)hipFuncSetAttribute((const void*)rf_predict_lds<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * RFP_TREE);
-    }
-    // one workgroup per CU (the LDS double buffer), rows spread evenly; at most 2 x 64 rows per wave
-    constexpr int NW = RFP_WAVES;
-    int64_t grid = (N + 64 * NW - 1) / (64 * NW);
-    if (grid > cus) grid = cus;
-    int64_t rpw = ((N + grid - 1) / grid + NW - 1) / NW;
-    if (rpw > 128) {
-      rpw = 128;
-      grid = (N + NW * rpw - 1) / (NW * rpw);
-    }
-    const int G = (int)((rpw + 63) / 64);
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), 2 * RFP_TREE, stream, X, N, (const uint8_t*)prep,
-                         T, (int)rpw, NW * rpw, out_logit, out, ldo);
-    };
-    if (G == 1) go(rf_predict_lds<1>);
-    else go(rf_predict_lds<2>);
-    EM_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL(rf_predict, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, X, W, N, feat, value, T, nodes,
-                     out_logit, out, ldo);
+  const int rc = rf_predict_streamed(false, X, W, N, feat, value, T, max_depth, out_logit, 0, 0, out, ldo, nullptr, prep, stream);
+  if (rc != RF_NOT_STREAMED) return rc;
+  hipLaunchKernelGGL(rf_predict<false>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, X, W, N, feat, value, T,
+                     (1 << (max_depth + 1)) - 1, out_logit, (uint64_t)0, 0, out, ldo, (int32_t*)nullptr);
   EM_CHECK_LAUNCH();
   return 0;
 }
@@ -1706,41 +1604,10 @@ EM_API int em_rf_oob_predict(const uint64_t* X, int W, int64_t N, const int16_t*
       max_depth > 14 || t_off < 0 || (int64_t)T + (int64_t)t_off > 0x7FFFFFFFll)
     return EM_ERR_ARG;
   if (N == 0) return 0;
-  const int nodes = (1 << (max_depth + 1)) - 1;
-  if (prep && em_rf_predict_scratch(W, T, max_depth) > 0 && ((uintptr_t)prep & 15) == 0 && (ldo & 3) == 0 &&
-      ((uintptr_t)out & 15) == 0) {
-    hipLaunchKernelGGL(rf_predict_prepare, dim3(T), dim3(RFP_PREP_THREADS), 0, stream, feat, value, nodes, max_depth, (uint8_t*)prep);
-    EM_CHECK_LAUNCH();
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          cus <= 0)
-        cus = 256;
-      (void)hipFuncSetAttribute((const void*)rf_oob_predict_lds<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * RFP_TREE);
-      (void)hipFuncSetAttribute((const void*)rf_oob_predict_lds<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * RFP_TREE);
-    }
-    // em_rf_predict's shape: one workgroup per CU, rows spread evenly, at most 2 x 64 rows per wave
-    constexpr int NW = RFP_WAVES;
-    int64_t grid = (N + 64 * NW - 1) / (64 * NW);
-    if (grid > cus) grid = cus;
-    int64_t rpw = ((N + grid - 1) / grid + NW - 1) / NW;
-    if (rpw > 128) {
-      rpw = 128;
-      grid = (N + NW * rpw - 1) / (NW * rpw);
-    }
-    const int G = (int)((rpw + 63) / 64);
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), 2 * RFP_TREE, stream, X, N, (const uint8_t*)prep,
-                         T, (int)rpw, NW * rpw, seed, t_off, out, ldo, count);
-    };
-    if (G == 1) go(rf_oob_predict_lds<1>);
-    else go(rf_oob_predict_lds<2>);
-    EM_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL(rf_oob_predict, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, X, W, N, feat, value, T, nodes,
-                     seed, t_off, out, ldo, count);
+  const int rc = rf_predict_streamed(true, X, W, N, feat, value, T, max_depth, 0, seed, t_off, out, ldo, count, prep, stream);
+  if (rc != RF_NOT_STREAMED) return rc;
+  hipLaunchKernelGGL(rf_predict<true>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, X, W, N, feat, value, T,
+                     (1 << (max_depth + 1)) - 1, 0, seed, t_off, out, ldo, count);
   EM_CHECK_LAUNCH();
   return 0;
 }

@@ -73,11 +73,11 @@ def fit(X: np.ndarray | torch.Tensor, Y: np.ndarray | torch.Tensor, F: int, t_of
     return feat.cpu().numpy(), value.cpu().numpy(), gain.cpu().numpy(), cover.cpu().numpy()
 
 
-def predict(X, feat, value, max_depth: int, out_logit: bool = False, device="cuda", stream_trees: bool = True
-            ) -> torch.Tensor:
-    """K11: mean leaf vector per row -> [N, 64] fp32 (probabilities, or logits if out_logit).
-    ``stream_trees``: single-word rows and depth <= 8 stream the trees through LDS (csrc/forest.hip
-    rf_predict_lds, bit-identical); False forces the one-wave-per-row kernel."""
+def _predict_args(X, feat, value, max_depth: int, stream_trees: bool, device):
+    """What predict and oob_predict share: X, feat and value on the device, the shape check, ``out`` [N, 64] and
+    the tree-image scratch.  Returns the leading arguments of either entry point (X, W, N, feat, value, T,
+    max_depth), ``out``, the scratch pointer (None: one wave per row), the stream, and the tensors behind the
+    pointers for the caller to hold until its launch is queued."""
     dev = torch.device(device)
     Xd = X if isinstance(X, torch.Tensor) else _u64_to_device(X, dev)
     n = Xd.shape[0]
@@ -90,8 +90,17 @@ def predict(X, feat, value, max_depth: int, out_logit: bool = False, device="cud
     out = torch.empty(n, 64, dtype=torch.float32, device=dev)
     nb = N.lib().em_rf_predict_scratch(W, T, max_depth) if stream_trees else 0
     prep = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev) if nb > 0 else None
-    N.call("em_rf_predict", Xd.data_ptr(), W, n, fd.data_ptr(), vd.data_ptr(), T, max_depth, int(out_logit),
-           out.data_ptr(), 64, prep.data_ptr() if prep is not None else None, N.stream_handle(dev))
+    head = (Xd.data_ptr(), W, n, fd.data_ptr(), vd.data_ptr(), T, max_depth)
+    return head, out, prep.data_ptr() if prep is not None else None, N.stream_handle(dev), (Xd, fd, vd, prep)
+
+
+def predict(X, feat, value, max_depth: int, out_logit: bool = False, device="cuda", stream_trees: bool = True
+            ) -> torch.Tensor:
+    """K11: mean leaf vector per row -> [N, 64] fp32 (probabilities, or logits if out_logit).
+    ``stream_trees``: single-word rows and depth <= 8 stream the trees through LDS (csrc/forest.hip
+    rf_predict_lds, bit-identical); False forces the one-wave-per-row kernel."""
+    head, out, prep, st, _keep = _predict_args(X, feat, value, max_depth, stream_trees, device)
+    N.call("em_rf_predict", *head, int(out_logit), out.data_ptr(), 64, prep, st)
     return out
 
 
@@ -100,23 +109,11 @@ def oob_predict(X, feat, value, max_depth: int, seed: int, t_off: int = 0, strea
     """K11-OOB: per row the mean leaf vector over the trees it is out of bag for -> (out [N, 64] fp32, count [N]
     int32).  ``X`` must be the matrix trees ``t_off .. t_off + T - 1`` (global ids) were fitted on with ``seed``:
     the in-bag sets are recomputed from the hash of (seed, tree id, row).  Rows without an out-of-bag tree are
-    all zero with count 0.  ``stream_trees`` as :func:`predict` (rf_oob_predict_lds, bit-identical)."""
-    dev = torch.device(device)
-    Xd = X if isinstance(X, torch.Tensor) else _u64_to_device(X, dev)
-    n = Xd.shape[0]
-    W = Xd.shape[1] if Xd.dim() == 2 else 1
-    fd = feat if isinstance(feat, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feat)).to(dev)
-    vd = value if isinstance(value, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(value)).to(dev)
-    T = fd.shape[0]
-    if fd.shape[1] != (1 << (max_depth + 1)) - 1:
-        raise ValueError("feat does not match max_depth")
-    out = torch.empty(n, 64, dtype=torch.float32, device=dev)
-    count = torch.empty(n, dtype=torch.int32, device=dev)
-    nb = N.lib().em_rf_predict_scratch(W, T, max_depth) if stream_trees else 0
-    prep = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev) if nb > 0 else None
-    N.call("em_rf_oob_predict", Xd.data_ptr(), W, n, fd.data_ptr(), vd.data_ptr(), T, max_depth,
-           int(seed) & 0xFFFFFFFFFFFFFFFF, int(t_off), out.data_ptr(), 64, count.data_ptr(),
-           prep.data_ptr() if prep is not None else None, N.stream_handle(dev))
+    all zero with count 0.  ``stream_trees`` as :func:`predict` (rf_predict_lds<G, OOB>, bit-identical)."""
+    head, out, prep, st, _keep = _predict_args(X, feat, value, max_depth, stream_trees, device)
+    count = torch.empty(out.shape[0], dtype=torch.int32, device=out.device)
+    N.call("em_rf_oob_predict", *head, int(seed) & 0xFFFFFFFFFFFFFFFF, int(t_off), out.data_ptr(), 64,
+           count.data_ptr(), prep, st)
     return out, count
 
 

@@ -1,5 +1,5 @@
-"""Random forest out-of-bag evaluation on the device (csrc/forest.hip K11-OOB: rf_oob_predict,
-rf_oob_predict_lds, rf_oob_metrics) against the fp64 reference written from the definition
+"""Random forest out-of-bag evaluation on the device (csrc/forest.hip K11-OOB: rf_predict<true>,
+rf_predict_lds<G, true>, rf_oob_metrics) against the fp64 reference written from the definition
 (tests/_rf_oob_ref.py).  The forests are the numpy engine's (shared with tests/test_rf_oob_cpu.py), so
 every difference is the OOB kernels'."""
 import numpy as np
@@ -37,6 +37,47 @@ def test_device_oob_matches_reference(name):
         worst = R.check_oob(out.cpu().numpy(), cnt.cpu().numpy(), rp, rc)
         print(f"{name}: worst error / budget {worst:.3f}, zero-count rows {int((rc == 0).sum())}")
     assert torch.equal(out_s, out_g) and torch.equal(cnt_s, cnt_g)
+
+
+@pytest.mark.parametrize("depth,trees,n,t_off", [(8, 100, 200001, 0), (3, 37, 600000, 5)])
+def test_device_oob_streamed_two_row_groups(depth, trees, n, t_off):
+    """The streamed kernel with two row groups per wave (every case above has at most 3000 rows: one group)
+    equals the one-wave-per-row kernel bit for bit, `out` and `count`; `count` equals the specification's
+    (models/forest.py poisson_weights == 0, summed over the trees); outputs 62 / 63 and zero-count rows are
+    zero.  On 256 CUs: 66 rows per wave (the second group holds 2 live lanes in most waves and none in the
+    last), and 128 rows per wave on a grid past one workgroup per CU with a tree offset.  The out-of-bag sets
+    depend on (seed, tree id, row) only, so the trees need not have been fitted on these rows."""
+    import torch
+
+    from euromillioner_amd.data.draws import mask_bits
+    from euromillioner_amd.data.synthetic import generate_draws
+    from euromillioner_amd.models.forest import poisson_weights
+    from euromillioner_amd.ops import forest as K
+
+    # the launcher's shape (csrc/forest.hip rf_predict_streamed): 12 waves, one workgroup per CU, <= 128 rows per wave
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    grid = min(-(-n // (64 * 12)), cus)
+    rows_per_wave = min(-(-(-(-n // grid)) // 12), 128)
+    if rows_per_wave <= 64:
+        pytest.skip(f"{cus} CUs give {rows_per_wave} rows per wave at {n} rows: one row group")
+    seed = 3
+    nums, _ = generate_draws(20001, seed=1, planted=0.9, native=False)
+    md = torch.from_numpy(mask_bits(nums).view(np.int64)).cuda()
+    n_tr = 14000
+    feat, value, _, _ = K.fit(md[:n_tr].reshape(-1, 1).contiguous(), md[1:n_tr + 1].contiguous(), 62, t_off, trees,
+                              depth, 8, 1, True, seed, return_device=True)
+    g = torch.Generator(device="cuda").manual_seed(n)
+    Xv = md[torch.randint(0, 20000, (n,), device="cuda", generator=g)].reshape(-1, 1).contiguous()
+    out_s, cnt_s = K.oob_predict(Xv, feat, value, depth, seed, t_off, stream_trees=True)
+    out_g, cnt_g = K.oob_predict(Xv, feat, value, depth, seed, t_off, stream_trees=False)
+    assert torch.equal(out_s, out_g) and torch.equal(cnt_s, cnt_g)
+    spec = np.zeros(n, dtype=np.int32)
+    for t in range(trees):
+        spec += poisson_weights(seed, t_off + t, n) == 0
+    cnt = cnt_s.cpu().numpy()
+    print(f"rows per wave {rows_per_wave}, count {cnt.min()}..{cnt.max()}, zero-count rows {int((cnt == 0).sum())}")
+    assert np.array_equal(cnt, spec)
+    assert bool((out_s[:, 62:] == 0).all()) and bool((out_s[cnt_s == 0] == 0).all())
 
 
 @pytest.mark.parametrize("name", ["d5", "t3_d8", "n1537"])
