@@ -10,6 +10,7 @@ runs the whole pipeline (``Main.java:35``).  Here:
     euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv] [--tickets 5 --temperature 1.0]
     euromillioner backtest --ckpt model.zip --tickets 16   # prize tiers of sampled tickets on the validation split
     euromillioner explain --ckpt model.json [--top 3]      # which of the last draw's numbers push each GBDT pick (TreeSHAP)
+    euromillioner explain --ckpt forest.npz [--top 3]      # the same for a forest checkpoint, over its last `lags` draws
     euromillioner gen --n 1000000 --planted 0.9 --out draws.csv
     euromillioner info                 # device, native libraries, kernel inventory
 
@@ -91,7 +92,7 @@ def build_parser() -> argparse.ArgumentParser:
     p = sub.add_parser("backtest", help="play sampled tickets on every validation draw and count prize tiers")
     _add_common(p)
     p.add_argument("--model", default=None, choices=["mlp", "mlp-wide"])
-    p = sub.add_parser("explain", help="TreeSHAP: the features behind each number a GBDT checkpoint picks")
+    p = sub.add_parser("explain", help="TreeSHAP: the features behind each number a GBDT (.json) or forest (.npz) checkpoint picks")
     _add_common(p)
     p.add_argument("--top", type=int, default=3, help="features listed per picked number")
     p = sub.add_parser("gen", help="write synthetic draws to CSV")

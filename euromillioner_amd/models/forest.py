@@ -127,6 +127,7 @@ class RandomForest:
         self.backend_used = None
         self.n_train = None  # rows of the last fit (None: unknown, e.g. an older forest file)
         self.tree_start = 0  # global id of tree 0 (fit with an explicit trees= range)
+        self.explain_backend_used = None  # numpy | hip: what the last predict_contribs / apply ran on
 
     # ------------------------------------------------------------------ fit
     def _backend(self) -> str:
@@ -263,6 +264,96 @@ class RandomForest:
         from .forest_oob import feature_importances
 
         return feature_importances(self, kind)
+
+    # ------------------------------------------------------------------ explanations (models/forest_explain.py)
+    def _explain_backend(self, backend, need_plan: bool) -> str:
+        """numpy | hip for an explanation call.  ``None``: HIP when a GPU is present (and, for contributions,
+        the forest is inside the device plan), else numpy.  ``"hip"`` outside the plan raises."""
+        if backend not in (None, "numpy", "hip"):
+            raise ValueError(f"backend must be None, 'numpy' or 'hip', got {backend!r}")
+        if backend == "numpy":
+            return "numpy"
+        if backend is None and self._backend() != "hip":
+            return "numpy"
+        if need_plan:
+            from ..ops import forest as K
+
+            if not K.shap_plan(self.F, self.max_depth):
+                if backend == "hip":
+                    raise ValueError(f"GPU TreeSHAP: no plan for max_depth {self.max_depth} with {self.F} features "
+                                     f"(the plan covers max_depth <= 8 and F <= 256)")
+                return "numpy"
+        return "hip"
+
+    def _shap_tables(self):
+        """The device path table (em_rf_shap_paths), built once per fitted forest."""
+        from ..ops import forest as K
+        from . import forest_explain as E
+
+        cached = getattr(self, "_shap_device", None)
+        if cached is not None and cached[0] is self.feat:
+            return cached[1]
+        E.paths_of(self)  # validates on the host: the kernels index by feat and assume distinct path features
+        tables = K.shap_tables(self.feat, self.value, self.cover, E.leaf_mask(self.feat), self.max_depth, self.F)
+        self._shap_device = (self.feat, tables)
+        return tables
+
+    def _check_rows(self, X):
+        if self.feat is None:
+            raise ValueError("the forest is not fitted")
+        X = np.asarray(X, dtype=np.uint64).reshape(len(X), -1)
+        W = (self.F + 63) // 64
+        if X.shape[1] < W:
+            raise ValueError(f"X has {X.shape[1]} feature words, the forest needs {W}")
+        return np.require(X[:, :W], requirements=["C", "W"])  # (a read-only input is copied: torch wants writable)
+
+    def predict_contribs_device(self, X):
+        """:meth:`predict_contribs` on the GPU, as a [n, 62, F+1] fp32 device tensor (no host copy, no chunks)."""
+        from ..ops import forest as K
+
+        self.explain_backend_used = self._explain_backend("hip", need_plan=True)
+        return K.shap(self._check_rows(X), self._shap_tables())
+
+    def predict_contribs(self, X: np.ndarray, backend: str | None = None, chunk_rows: int | None = None) -> np.ndarray:
+        """float32 ``[n, 62, F+1]`` path-dependent TreeSHAP contributions of :meth:`predict_proba` on packed rows
+        ``X`` [n, W], the bias (the forest's expectation under its covers) in the last column:
+        ``phi[r, o, :F].sum() + phi[r, o, F] == predict_proba[r, o]`` up to rounding.  ``backend``: None | numpy |
+        hip.  On the GPU the rows go through the kernel ``chunk_rows`` at a time; a row's result depends on the
+        row only."""
+        from . import forest_explain as E
+
+        X = self._check_rows(X)
+        self.explain_backend_used = self._explain_backend(backend, need_plan=True)
+        if self.explain_backend_used == "numpy":
+            return E.contribs_numpy(self, X).astype(np.float32)
+        from ..ops import forest as K
+
+        tables = self._shap_tables()
+        n, row_bytes = len(X), 62 * (self.F + 1) * 4
+        if chunk_rows is None:
+            chunk_rows = max(256, (256 << 20) // row_bytes)
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("chunk_rows must be positive")
+        out = np.empty((n, 62, self.F + 1), dtype=np.float32)
+        for a in range(0, n, chunk_rows):
+            out[a:a + chunk_rows] = K.shap(X[a:a + chunk_rows], tables).cpu().numpy()
+        return out
+
+    def apply(self, X: np.ndarray, backend: str | None = None) -> np.ndarray:
+        """int32 ``[n, T]``: the heap index of the leaf each row stops at in each tree (sklearn's ``apply``)."""
+        from . import forest_explain as E
+
+        X = self._check_rows(X)
+        self.explain_backend_used = self._explain_backend(backend, need_plan=False)
+        if self.explain_backend_used == "numpy":
+            return E.apply_numpy(self, X)
+        from ..ops import forest as K
+
+        E.paths_of(self)  # (validation: the kernel indexes the row's words by feat)
+        if len(X) == 0:
+            return np.zeros((0, len(self.feat)), dtype=np.int32)
+        return K.leaf_index(X, self.feat, self.max_depth, self.F).cpu().numpy()
 
     # ------------------------------------------------------------------ persistence (T6 tree file)
     def meta(self) -> dict:

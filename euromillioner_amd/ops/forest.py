@@ -1,5 +1,6 @@
 """Python face of the random-forest kernels (``csrc/forest.hip``: K8 hist, K9 split scan,
-K10 partition, K11 predict, K11-OOB out-of-bag predict and metrics) and their native level-wise driver ``em_rf_fit``.
+K10 partition, K11 predict, K11-OOB out-of-bag predict and metrics) and their native level-wise driver ``em_rf_fit``,
+and of the explanation kernels (``csrc/forest_shap.hip``: TreeSHAP contributions, leaf indices).
 
 The reference only declares Spark MLlib's RandomForest (``/root/reference/pom.xml:56-61``,
 ``README.md:6``); SURVEY.md §2.4 N7 / BASELINE config 4 define the 100-tree one-hot forest."""
@@ -26,6 +27,11 @@ N.register_signatures({
                                    N._c_void_p]),
     "em_rf_oob_metrics_words": (N._i64, [N._i64]),
     "em_rf_oob_metrics": (N._i32, [N._c_void_p, N._i32, N._c_void_p, N._c_void_p, N._i64, N._c_void_p, N._c_void_p]),
+    "em_rf_shap_lds_bytes": (N._i32, [N._i32, N._i32]),
+    "em_rf_shap_paths": (N._i32, [N._i32, N._i32, N._i32, N._i32] + [N._c_void_p] * 11),
+    "em_rf_shap": (N._i32, [N._c_void_p, N._i32, N._i32, N._i32, N._i32, N._i32, N._i32] + [N._c_void_p] * 7),
+    "em_rf_leaf_index": (N._i32, [N._c_void_p, N._i32, N._i64, N._i32, N._c_void_p, N._i32, N._i32, N._c_void_p,
+                                  N._c_void_p]),
 })
 
 
@@ -150,3 +156,76 @@ def oob_metrics(out: torch.Tensor, count: torch.Tensor, Y) -> dict:
     from ..models.forest_oob import oob_finish
 
     return oob_finish(oob_totals(out, count, Y))
+
+
+# ----------------------------------------------------------------------------- explanations (csrc/forest_shap.hip)
+class ShapTables:
+    """The device leaf-path table of a forest (em_rf_shap_paths) and its bias row."""
+
+    def __init__(self, T, L, max_depth, F, pd, pf, pz, pval, bias):
+        self.T, self.L, self.max_depth, self.F = T, L, max_depth, F
+        self.pd, self.pf, self.pz, self.pval, self.bias = pd, pf, pz, pval, bias
+
+
+def shap_plan(F: int, max_depth: int) -> bool:
+    """Whether the contribution kernel covers the shape (max_depth <= 8, F <= 256)."""
+    return N.query("em_rf_shap_lds_bytes", int(F), int(max_depth)) >= 0
+
+
+def shap_tables(feat: np.ndarray, value: np.ndarray, cover: np.ndarray, leaves: np.ndarray, max_depth: int, F: int,
+                device="cuda") -> ShapTables:
+    """Build the path table of a validated forest on the device.  ``leaves`` is the bool [T, nodes] mask of its
+    leaves (``forest_explain.leaf_mask``): the host fixes each leaf's place in the table, the kernel fills it."""
+    dev = torch.device(device)
+    T, NN = feat.shape
+    leaves = np.asarray(leaves, dtype=bool)
+    L = int(leaves.sum())
+    slot = np.where(leaves.reshape(-1), np.cumsum(leaves.reshape(-1)) - 1, -1).astype(np.int32)
+    S = max(1, int(max_depth))
+    d_slot = torch.from_numpy(slot).to(dev)
+    fd = torch.from_numpy(np.ascontiguousarray(feat, dtype=np.int16)).to(dev)
+    vd = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float32)).to(dev)
+    cd = torch.from_numpy(np.ascontiguousarray(cover, dtype=np.float32)).to(dev)
+    pd = torch.empty(L, dtype=torch.int32, device=dev)
+    pf = torch.empty(L, dtype=torch.int64, device=dev)  # 8 feature bytes per leaf
+    pz = torch.empty(L * S, dtype=torch.float32, device=dev)
+    pval = torch.empty(L, 64, dtype=torch.float32, device=dev)
+    pbias = torch.empty(L, 64, dtype=torch.float64, device=dev)
+    bias = torch.empty(64, dtype=torch.float32, device=dev)
+    N.call("em_rf_shap_paths", T, int(max_depth), int(F), L, d_slot.data_ptr(), fd.data_ptr(), vd.data_ptr(),
+           cd.data_ptr(), pd.data_ptr(), pf.data_ptr(), pz.data_ptr(), pval.data_ptr(), pbias.data_ptr(),
+           bias.data_ptr(), N.stream_handle(dev))
+    torch.cuda.synchronize(dev)  # (the inputs and pbias are released here)
+    return ShapTables(T, L, int(max_depth), int(F), pd, pf, pz, pval, bias)
+
+
+def shap(X, tables: ShapTables, out: torch.Tensor | None = None) -> torch.Tensor:
+    """em_rf_shap: [n, 62, F+1] fp32 contributions (bias last) of packed rows ``X`` [n, W] on the device."""
+    dev = tables.pd.device
+    Xd = X if isinstance(X, torch.Tensor) else _u64_to_device(np.asarray(X).reshape(len(X), -1), dev)
+    n = Xd.shape[0]
+    W = Xd.shape[1] if Xd.dim() == 2 else 1
+    if out is None:
+        out = torch.empty(n, 62, tables.F + 1, dtype=torch.float32, device=dev)
+    elif out.shape != (n, 62, tables.F + 1) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 [n, 62, F+1]")
+    N.call("em_rf_shap", Xd.data_ptr(), W, n, tables.F, tables.max_depth, tables.T, tables.L, tables.pd.data_ptr(),
+           tables.pf.data_ptr(), tables.pz.data_ptr(), tables.pval.data_ptr(), tables.bias.data_ptr(), out.data_ptr(),
+           N.stream_handle(dev))
+    return out
+
+
+def leaf_index(X, feat, max_depth: int, F: int, device="cuda") -> torch.Tensor:
+    """em_rf_leaf_index: [n, T] int32 heap index of the node each row stops at in each tree."""
+    dev = torch.device(device)
+    Xd = X if isinstance(X, torch.Tensor) else _u64_to_device(np.asarray(X).reshape(len(X), -1), dev)
+    n = Xd.shape[0]
+    W = Xd.shape[1] if Xd.dim() == 2 else 1
+    fd = feat if isinstance(feat, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feat, dtype=np.int16)).to(dev)
+    T = fd.shape[0]
+    if fd.shape[1] != (1 << (max_depth + 1)) - 1:
+        raise ValueError("feat does not match max_depth")
+    out = torch.empty(n, T, dtype=torch.int32, device=dev)
+    N.call("em_rf_leaf_index", Xd.data_ptr(), W, n, int(F), fd.data_ptr(), T, int(max_depth), out.data_ptr(),
+           N.stream_handle(dev))
+    return out

@@ -694,17 +694,20 @@ def gbdt_feature_names(n_features: int) -> list[str]:
 
 
 def explain_next(cfg: RunConfig, top: int = 3) -> dict:
-    """``euromillioner explain``: for each number and star a GBDT checkpoint picks for the next draw, the ``top``
-    features of the last draw with the largest |TreeSHAP contribution| to that pick's margin."""
+    """``euromillioner explain``: for each number and star a GBDT (.json) or forest (.npz) checkpoint picks for the
+    next draw, the ``top`` features with the largest |TreeSHAP contribution| to that pick's margin (GBDT) or
+    probability (forest)."""
     path = cfg.ckpt.resume or cfg.ckpt.path
     if not path:
-        raise ValueError("explain needs --ckpt (or --resume) pointing at a GBDT checkpoint")
+        raise ValueError("explain needs --ckpt (or --resume) pointing at a GBDT or forest checkpoint")
     if not os.path.exists(path):
         raise FileNotFoundError(path)
-    if not path.endswith(".json"):
-        raise ValueError(f"explain covers GBDT checkpoints (.json) only, not {os.path.basename(path)}")
+    if not path.endswith((".json", ".npz")):
+        raise ValueError(f"explain covers GBDT (.json) and forest (.npz) checkpoints only, not {os.path.basename(path)}")
     if top < 1:
         raise ValueError("--top must be at least 1")
+    if path.endswith(".npz"):
+        return _explain_forest(cfg, path, top)
     from .models.gbdt import GBDT
     from .models.gbdt_explain import num_features
     from .pipeline import _gbdt_backend
@@ -733,6 +736,37 @@ def explain_next(cfg: RunConfig, top: int = 3) -> dict:
                       "top": feats})
         print(f"{kind} {v:02d}: " + ", ".join(f"{d['feature']} {d['phi']:+.4f}" for d in feats))
     return {"model": "gbdt", "checkpoint": path, "backend": be, "main": main, "stars": stars,
+            "after_draw": date_str(ds.dates[-1]) if ds.dates is not None else None, "explain": picks}
+
+
+def _explain_forest(cfg: RunConfig, path: str, top: int) -> dict:
+    """The forest half of :func:`explain_next`: the input row is the last ``lags = F / 62`` draws, the picks are
+    the largest ``predict_proba`` entries (== ``phi.sum``), the features are named after ``lag_features``."""
+    from .models.forest import RandomForest, pack_bits
+    from .models.forest_explain import feature_names
+
+    ds = load_draws(cfg)
+    rf = RandomForest.load(path)
+    F = int(rf.F)
+    lags = F // 62
+    if lags < 1 or F != 62 * lags:
+        raise ValueError(f"explain needs a next-draw forest over 62 features per draw, this checkpoint has {F}")
+    if len(ds) < lags:
+        raise ValueError(f"the checkpoint expects {F} features ({lags} draws), the data gives {62 * len(ds)}")
+    x = pack_bits(multi_hot(ds.numbers[len(ds) - lags:]).reshape(1, -1))
+    # --device cpu: the numpy path; otherwise the device when there is one and the forest is inside its plan
+    phi = rf.predict_contribs(x, backend="numpy" if cfg.device == "cpu" else None)
+    phi, be = np.asarray(phi, dtype=np.float64)[0], rf.explain_backend_used  # [62, F+1]
+    main, stars = _top_pick(phi.sum(axis=1))  # sum == predict_proba
+    names = feature_names(F)
+    picks = []
+    for kind, v, t in [("number", v, v - 1) for v in main] + [("star", v, 49 + v) for v in stars]:
+        order = np.argsort(-np.abs(phi[t, :F]), kind="stable")[:top]
+        feats = [{"feature": names[f], "index": int(f), "phi": round(float(phi[t, f]), 6)} for f in order]
+        picks.append({"pick": f"{kind} {v}", "proba": round(float(phi[t].sum()), 6), "bias": round(float(phi[t, F]), 6),
+                      "top": feats})
+        print(f"{kind} {v:02d}: " + ", ".join(f"{d['feature']} {d['phi']:+.4f}" for d in feats))
+    return {"model": "rf", "checkpoint": path, "backend": be, "main": main, "stars": stars,
             "after_draw": date_str(ds.dates[-1]) if ds.dates is not None else None, "explain": picks}
 
 
