@@ -16,7 +16,7 @@
 //   K11 gbdt_predict    ensemble traversal over binned rows
 //   K13 gbdt_metric     logloss / rmse / error partial sums -> per-round history
 // Node numbering is heap order (children 2i+1, 2i+2); status 0 unused / 1 split / 2 leaf.
-#include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -1575,6 +1575,10 @@ inline int grid_for(int64_t total, int bs = 256) {
   if (g > 4096) g = 4096;
   return (int)(g < 1 ? 1 : g);
 }
+inline int launch_status() {  // 0, or the error of a launch enqueued since the last look
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? (int)e : 0;
+}
 
 }  // namespace
 
@@ -1682,15 +1686,34 @@ struct HistPartition {  // the previous level's partition fused into the exact-f
   const uint8_t* sb = nullptr;
   int NN = 0;
 };
-int launch_level_hist(int level, const uint8_t* bins, const float* g, const float* h, const int16_t* node, int T,
-                      int n, int F, const int* foff_h, const int* foff_d, double* partial, int64_t partial_doubles,
-                      bool fold, double qscale, int* nchunks_out, hipStream_t stream, const QuantAux* qa = nullptr,
-                      const HistPartition& hp = HistPartition(), const HistUpdate* hu = nullptr,
-                      const HistSplit* hsp = nullptr, size_t min_lds = 0, const HistPre* pre = nullptr) {
+// One level's histogram launch: what every form takes, then the optional parts (of the exact form, but for qa)
+struct LevelHist {
+  int level, T, n, F;
+  const uint8_t* bins;
+  const float *g, *h;
+  const int16_t* node;
+  const int *foff_h, *foff_d;
+  double* partial;
+  int64_t partial_doubles;
+  bool fold;
+  double qscale;                          // != 0: fixed point
+  const QuantAux* qa = nullptr;           // ... in the sparse form
+  HistPartition partition = {};           // levels >= 1 of the fused round
+  const HistUpdate* update = nullptr;     // level 0: the previous round's update and this round's start
+  const HistSplit* root_split = nullptr;  // level 0: the root split by each task's last-arriving block
+  const HistPre* pre = nullptr;           // the previous level's split in the leading blocks
+  size_t min_lds = 0;                     // (root_split and pre run in the histogram's LDS)
+};
+int launch_level_hist(const LevelHist& a, int* nchunks_out, hipStream_t stream) {
+  const int level = a.level, T = a.T, n = a.n, F = a.F, C = a.foff_h[F], nodesL = 1 << level;
+  const int *foff_h = a.foff_h, *foff_d = a.foff_d;
+  const QuantAux* qa = a.qa;
+  const HistUpdate* hu = a.update;
+  const HistPre* pre = a.pre;
+  const double qscale = a.qscale;
   const bool quant = qscale != 0.0;
-  const int C = foff_h[F];
-  const int nodesL = 1 << level;
   const int64_t S = (int64_t)T * nodesL * C * 2;
+  double* partial = a.partial;
   long long* qpart = reinterpret_cast<long long*>(partial);
   int nchunks = 0;
   if (quant && qa && qa->nb > 0) {
@@ -1700,51 +1723,49 @@ int launch_level_hist(int level, const uint8_t* bins, const float* g, const floa
     const int64_t per_chunk = (int64_t)T * (nodesL / NTb);  // ~4096 blocks per level
     const int64_t want = (4096 + per_chunk - 1) / per_chunk;
     int64_t chunk = (n + want - 1) / want;
-    const int64_t maxch = partial_doubles / S;  // chunks that fit the partial buffer
+    const int64_t maxch = a.partial_doubles / S;  // chunks that fit the partial buffer
     if (maxch < 1) return EM_ERR_ARG;
     if ((n + chunk - 1) / chunk > maxch) chunk = (n + maxch - 1) / maxch;
     if (chunk < 64) chunk = 64;
     nchunks = (int)((n + chunk - 1) / chunk);
     hipLaunchKernelGGL(gbdt_hist_qb, dim3(nchunks, T, nodesL / NTb), dim3(256), (size_t)2 * NTb * NWb * 8, stream,
-                       qa->bmask_d, qa->WB, qa->bcell_d, qa->nb, bins, F, qa->fmap_d, qa->foffm_d, foff_d, qa->Fm, g,
-                       h, node, qpart, T, n, C, level, (int)chunk, NTb, qscale);
+                       qa->bmask_d, qa->WB, qa->bcell_d, qa->nb, a.bins, F, qa->fmap_d, qa->foffm_d, foff_d, qa->Fm,
+                       a.g, a.h, a.node, qpart, T, n, C, level, (int)chunk, NTb, qscale);
   } else {
     HistPlan pl;
     if (!plan_hist(level, n, T, F, foff_h, quant, pl)) return EM_ERR_ARG;
-    if ((int64_t)pl.nchunks * S > partial_doubles) return EM_ERR_ARG;
+    if ((int64_t)pl.nchunks * S > a.partial_doubles) return EM_ERR_ARG;
     nchunks = pl.nchunks;
     // (hu: level 0 with one tile per (chunk, task); eval sets on extra z planes)
     if (hu && (quant || level != 0 || pl.nft * pl.ntn != 1)) return EM_ERR_ARG;
-    if (pre && (quant || hu || hsp)) return EM_ERR_ARG;
+    if (pre && (quant || hu || a.root_split)) return EM_ERR_ARG;
     HistPre pr = pre ? *pre : HistPre();
     if (pre) pr.nz = (pr.nodes + pl.nchunks - 1) / pl.nchunks;  // split planes in front of the histogram's
     const dim3 grid(pl.nchunks, T, pr.nz + pl.nft * pl.ntn + (hu && hu->apply ? hu->evs.count : 0));
     if (quant)
-      hipLaunchKernelGGL(gbdt_hist_q, grid, dim3(pl.threads), pl.lds, stream, bins, g, h, node, foff_d,
+      hipLaunchKernelGGL(gbdt_hist_q, grid, dim3(pl.threads), pl.lds, stream, a.bins, a.g, a.h, a.node, foff_d,
                          (const int*)nullptr, foff_d, qpart, T, n, F, F, C, level, pl.chunk, pl.FT, pl.NTn, pl.P,
                          pl.ldsC, pl.piece, qscale);
-    else
-    {
+    else {
       // exact form: the previous level's split arrays (partition fused in) and, when a piece's bin rows
       // fit 16 KB, the rows themselves are staged in LDS after the (g, h, node) staging
       const int srows = pl.piece < pl.chunk ? pl.piece : pl.chunk;
+      const HistPartition& hp = a.partition;
       const int npn = hp.node_out ? (1 << level) - (1 << (level - 1)) : 0;
       size_t lds = ((pl.lds + 15) & ~(size_t)15) + (((size_t)npn * 4 + 15) & ~(size_t)15);
       const size_t sbytes = (((size_t)srows * F + 32 + 15) & ~(size_t)15);
       const int stage = ((int64_t)srows * F <= 16 * 1024 && lds + sbytes <= GBDT_HIST_MAX_DYN) ? srows : 0;
       if (stage) lds += sbytes;
-      if (lds < min_lds) lds = min_lds;  // (the fused root split reuses the histogram's LDS)
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gbdt_hist, hipFuncAttributeMaxDynamicSharedMemorySize, GBDT_HIST_MAX_DYN);
-        attr = true;
-      }
-      hipLaunchKernelGGL(gbdt_hist, grid, dim3(pl.threads), lds, stream, bins, g, h, node, foff_d, partial, T, n, F,
-                         C, level, pl.chunk, pl.FT, pl.NTn, pl.P, pl.ldsC, pl.piece, stage, hp.node_out, hp.st, hp.fe,
-                         hp.sb, hp.NN, hu ? *hu : HistUpdate(), hsp ? *hsp : HistSplit(), pr);
+      if (lds < a.min_lds) lds = a.min_lds;  // (the fused root split reuses the histogram's LDS)
+      static const hipError_t attr =
+          hipFuncSetAttribute((const void*)gbdt_hist, hipFuncAttributeMaxDynamicSharedMemorySize, GBDT_HIST_MAX_DYN);
+      (void)attr;
+      hipLaunchKernelGGL(gbdt_hist, grid, dim3(pl.threads), lds, stream, a.bins, a.g, a.h, a.node, foff_d, partial, T,
+                         n, F, C, level, pl.chunk, pl.FT, pl.NTn, pl.P, pl.ldsC, pl.piece, stage, hp.node_out, hp.st,
+                         hp.fe, hp.sb, hp.NN, hu ? *hu : HistUpdate(), a.root_split ? *a.root_split : HistSplit(), pr);
     }
   }
-  const bool split_folds = !fold && nchunks <= SPLIT_FOLD_MAX_CHUNKS && (int64_t)C * 16 <= SPLIT_FOLD_MAX_LDS;
+  const bool split_folds = !a.fold && nchunks <= SPLIT_FOLD_MAX_CHUNKS && (int64_t)C * 16 <= SPLIT_FOLD_MAX_LDS;
   if (nchunks > 1 && !split_folds) {
     if (quant)
       hipLaunchKernelGGL(gbdt_chunk_reduce<long long>, dim3(grid_for(S)), dim3(256), 0, stream, qpart, nchunks, S);
@@ -1752,8 +1773,7 @@ int launch_level_hist(int level, const uint8_t* bins, const float* g, const floa
       hipLaunchKernelGGL(gbdt_chunk_reduce<double>, dim3(grid_for(S)), dim3(256), 0, stream, partial, nchunks, S);
   }
   *nchunks_out = split_folds ? nchunks : 1;
-  EM_CHECK_LAUNCH();
-  return 0;
+  return launch_status();
 }
 
 bool valid_foff(const int* foff, int F) {
@@ -1763,60 +1783,31 @@ bool valid_foff(const int* foff, int F) {
   return true;
 }
 
-// [T] zeroed device ints (grown on demand; left zeroed by every use): gbdt_split's per-task arrival
-// counters of the fused finalize
-int* task_counters(int T) {
-  static int* ctr = nullptr;
-  static int cap = 0, dev = -1;
+// Zeroed device ints kept for the process (for the device in use): allocated at the first request, left zeroed
+// by every use, reallocated for a larger request; the words of a device no longer current are dropped.
+struct ZeroedInts { int* p = nullptr; int cap = 0, dev = -1; };
+int* zeroed_ints(ZeroedInts& z, int want) {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess) return nullptr;
-  if (!ctr || dev != d || T > cap) {
-    if (ctr && dev == d) {
-      (void)hipDeviceSynchronize();
-      (void)hipFree(ctr);
-    }
-    ctr = nullptr;
-    int* p = nullptr;
-    const int want = T > 1024 ? T : 1024;
-    if (hipMalloc(&p, (size_t)want * sizeof(int)) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, (size_t)want * sizeof(int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return nullptr;
-    ctr = p;
-    cap = want;
-    dev = d;
+  if (z.p && z.dev == d && want <= z.cap) return z.p;
+  if (z.p && z.dev == d) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(z.p);
   }
-  return ctr;
+  z.p = nullptr;
+  int* p = nullptr;
+  if (hipMalloc(&p, (size_t)want * sizeof(int)) != hipSuccess) return nullptr;
+  if (hipMemset(p, 0, (size_t)want * sizeof(int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return nullptr;
+  z = ZeroedInts{p, want, d};
+  return p;
 }
-// one zeroed device int per process (per device in use): the fused metric launches' arrival counter
-int* metric_counter() {
-  static int* ctr = nullptr;
-  static int dev = -1;
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess) return nullptr;
-  if (!ctr || dev != d) {
-    int* p = nullptr;
-    if (hipMalloc(&p, 64) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, 64) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return nullptr;
-    ctr = p;
-    dev = d;
-  }
-  return ctr;
-}
-// one zeroed device int per process (per device in use): raised by a histogram block whose HistPre poll timed
-// out (the fit's trees are then invalid); read and cleared by em_gbdt_fused_error
-int* fused_error_word() {
-  static int* w = nullptr;
-  static int dev = -1;
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess) return nullptr;
-  if (!w || dev != d) {
-    int* p = nullptr;
-    if (hipMalloc(&p, 64) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, 64) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return nullptr;
-    w = p;
-    dev = d;
-  }
-  return w;
-}
+// [T] (grown on demand): gbdt_split's per-task arrival counters of the fused finalize
+int* task_counters(int T) { static ZeroedInts z; return zeroed_ints(z, T > 1024 ? T : 1024); }
+// the fused metric launches' arrival counter
+int* metric_counter() { static ZeroedInts z; return zeroed_ints(z, 16); }
+// raised by a histogram block whose HistPre poll timed out (the fit's trees are then invalid); read and cleared
+// by em_gbdt_fused_error
+int* fused_error_word() { static ZeroedInts z; return zeroed_ints(z, 16); }
 }  // namespace
 
 // ------------------------------------------------------------------ C ABI
@@ -1840,11 +1831,386 @@ EM_API int64_t em_gbdt_partial_doubles(int n, int T, int F, const int* foff, int
   return need <= (int64_t(1) << 24) ? 2 * need : need;
 }
 
+// ------------------------------------------------------------------ em_gbdt_fit: plan, scratch, enqueue
+namespace {
+struct FitArgs {  // em_gbdt_fit's arguments, in its order
+  const uint8_t* bins;
+  const float* Y;
+  int n, F;
+  const int *foff_h, *foff_d;
+  int T;
+  float* margin;
+  const EmGbdtEval* evals;
+  int n_evals, r0, r1, max_depth, obj, metric;
+  float eta, lam, gamma, mcw, subsample;
+  uint32_t seed;
+  float *g, *h;
+  int16_t *node, *node2;
+  double* partial;
+  int64_t partial_doubles;
+  double *Gs, *Hs, *mpart;
+  int8_t* status;
+  int16_t* feat;
+  uint8_t* sbin;
+  float *leaf, *gainv, *cover, *hist_out;
+  int quant_bits, launch_flags;
+  hipStream_t stream;
+};
+
+// gbdt_split's dynamic LDS over `nch` chunk partials: the partials staged at once (oneshot) or one chunk's,
+// the parallel scan's area when it still fits beside them (+ the finalize area: < 64 KB), the finalize area
+struct SplitLds { int oneshot = 0, pscan = 0; size_t bytes = 0; };
+SplitLds split_lds(int nch, int C, int NN, bool with_final) {
+  const int oneshot = nch > 1 && (int64_t)nch * C * 16 <= SPLIT_ONESHOT_LDS;
+  const size_t part = nch > 1 ? (((size_t)(oneshot ? nch : 1) * C * 16 + 15) & ~(size_t)15) : 0;
+  const size_t scan_b = ((size_t)C * 20 + 15) & ~(size_t)15;
+  const int pscan = part + scan_b + (size_t)NN * 24 <= 60 * 1024;
+  return SplitLds{oneshot, pscan, part + (pscan ? scan_b : 0) + (with_final ? (size_t)NN * 24 : 0)};
+}
+
+// the eval sets as a kernel argument (mb: each set's blocks in the update launch; *blocks += their sum)
+EvalSets eval_sets(const EmGbdtEval* evals, int n_evals, int T, int* blocks = nullptr) {
+  EvalSets evs;
+  for (int e = 0; e < n_evals; ++e) {
+    evs.bins[e] = evals[e].bins, evs.margin[e] = evals[e].margin, evs.Y[e] = evals[e].Y, evs.n[e] = evals[e].n;
+    evs.mb[e] = grid_for((int64_t)T * evals[e].n);
+    if (blocks) *blocks += evs.mb[e];
+  }
+  evs.count = n_evals;
+  return evs;
+}
+
+// What one call decides before its first launch.  The round form by the arguments (elementwise metric: logloss,
+// rmse, error; per-task objective: not softmax; sets: train + eval sets; first matching row):
+//
+//   quant_bits  metric       depth  flags     objective  sets  round form
+//   > 0         any          any    any       any        any   separate launches over fixed-point histograms:
+//                                                              sparse (QuantAux, >= 8 one-hot features) or dense
+//   0           multi-class  any    any       any        any   separate launches, and update / metric / final sum
+//                                                              of the train and of each eval set one launch each
+//   0           elementwise  > 8 or SEPARATE  any        any   separate launches, metrics as in the fused round
+//   0           elementwise  <= 8   -         per-task   <= 5  fused round + hist_update: round r - 1's update in
+//                                                              round r's level-0 pass, with the root split when it
+//                                                              has 2 .. 32 chunks that fit the LDS (fsplit); one
+//                                                              update launch per call; deferred metrics
+//   0           elementwise  <= 8   -         per-task   > 5   fused round + next_in_update: round r + 1's start
+//                                                              in round r's update; the metrics every round, the
+//                                                              eval sets' by gbdt_predict_metric launches
+//   0           elementwise  <= 8   -         softmax    any   fused round, gbdt_round_start every round
+//   a fused round + PRESPLIT, depth >= 3, `partial` two levels wide: levels 1 .. depth - 2 split in the leading
+//                                                              blocks of the next level's pass (HistPre)
+//
+// hist_update also takes one histogram tile per (chunk, task) at level 0 and chunks x T <= 2^20; a fit without
+// either runs next_in_update with deferred metrics.  The fused round: the previous level's partition inside each
+// histogram pass (double-buffered nodes), the prune / leaves in the last level's split (last-arriving block per
+// task), the last partition in the update: 7 launches per depth-3 round instead of 13, bit-identical to the
+// separate launches.  Deferred metrics (<= 4 eval sets; metric_arrive_final with ctr == nullptr): every round's
+// per-block partials, reduced by gbdt_metric_rounds after the call's last round.  Presplit: bit-identical trees,
+// measured equal on the reference fit (profiles/r6/gbdt_presplit_ab.txt), so the split launches stay the default.
+struct FitPlan {
+  int NN = 0, C = 0, sets = 0;
+  int64_t TN = 0;
+  double qscale = 0.0, qinv = 0.0;
+  bool fuse = false, deferred = false, hist_update = false, next_in_update = false, presplit = false, fsplit = false;
+  int nch0 = 0;         // hist_update: the level-0 pass's chunks
+  int64_t mstride = 0;  // doubles between the sets' deferred partials
+  int64_t half = 0;     // doubles of `partial` one level may use (presplit: levels alternate between two halves)
+  SplitLds root;        // fsplit: the root split's LDS
+  int* mctr = nullptr;  // arrival counter of the fused metric launches (re-armed by each)
+  int* tctr = nullptr;  // fuse: [2 T] arrival counters of the fused finalize and the root split
+  int* perr = nullptr;  // presplit: the error word
+};
+
+bool make_plan(const FitArgs& a, FitPlan& p) {
+  p.qscale = a.quant_bits ? ldexp(1.0, a.quant_bits) : 0.0;
+  p.qinv = a.quant_bits ? ldexp(1.0, -a.quant_bits) : 0.0;
+  p.NN = (1 << (a.max_depth + 1)) - 1;
+  p.C = a.foff_h[a.F];
+  p.TN = (int64_t)a.T * a.n;
+  p.sets = 1 + a.n_evals;
+  if (!(p.mctr = metric_counter())) return false;
+  p.fuse = !(a.launch_flags & EM_GBDT_SEPARATE) && !a.quant_bits && a.metric < MET_MLOGLOSS &&
+           a.max_depth <= SPLIT_FINAL_MAX_DEPTH && a.node2 && (p.tctr = task_counters(2 * a.T)) != nullptr;
+  p.deferred = a.metric < MET_MLOGLOSS && a.n_evals <= 4;
+  p.mstride = grid_for(p.TN);
+  for (int e = 0; e < a.n_evals; ++e) p.mstride = std::max<int64_t>(p.mstride, grid_for((int64_t)a.T * a.evals[e].n));
+  HistPlan p0;
+  p.hist_update = p.fuse && a.obj != OBJ_SOFTMAX && p.deferred && plan_hist(0, a.n, a.T, a.F, a.foff_h, false, p0) &&
+                  p0.nft * p0.ntn == 1 && p0.nchunks * (int64_t)a.T <= (int64_t)1 << 20;
+  p.nch0 = p.hist_update ? p0.nchunks : 0;
+  if (p.hist_update && (int64_t)a.T * p.nch0 > p.mstride) p.mstride = (int64_t)a.T * p.nch0;
+  p.next_in_update = p.fuse && a.obj != OBJ_SOFTMAX && !p.hist_update;
+  p.fsplit = p.hist_update && p.nch0 > 1 && p.nch0 <= SPLIT_FOLD_MAX_CHUNKS &&
+             (int64_t)p.C * 16 <= SPLIT_FOLD_MAX_LDS && (int64_t)p.nch0 * p.C * 16 <= SPLIT_ONESHOT_LDS;
+  if (p.fsplit) p.root = split_lds(p.nch0, p.C, p.NN, a.max_depth == 1);
+  int64_t pneed = 0;  // presplit: the partial buffer must hold two levels' partials (double-buffered halves)
+  for (int l = 0; l < a.max_depth; ++l) pneed = std::max(pneed, partial_need(l, a.n, a.T, a.F, a.foff_h));
+  p.presplit = (a.launch_flags & EM_GBDT_PRESPLIT) && p.fuse && a.max_depth >= 3 && pneed > 0 &&
+               a.partial_doubles >= 2 * pneed;
+  p.half = p.presplit ? (a.partial_doubles / 2) & ~(int64_t)1 : a.partial_doubles;
+  p.perr = p.presplit ? fused_error_word() : nullptr;
+  return !p.presplit || p.perr;
+}
+
+// The call's device scratch under one owner.  qmem outlives every launch of the call: freed after the stream
+// drains.  The others are stream-ordered allocations, freed on the stream behind the last launch.
+struct FitScratch {
+  hipStream_t stream;
+  QuantAux qa;               // the sparse fixed-point form's tables (qa.nb > 0), in qmem
+  void* qmem = nullptr;
+  int4* cellinfo = nullptr;  // [C] direct split candidates, or none
+  double* mround = nullptr;  // deferred: [rounds][sets][mstride] metric partials
+  int* sctr = nullptr;       // presplit: [T] cumulative split arrivals of this fit
+  explicit FitScratch(hipStream_t s) : stream(s) {}
+  FitScratch(const FitScratch&) = delete;
+  ~FitScratch() {
+    if (sctr) (void)hipFreeAsync(sctr, stream);
+    if (mround) (void)hipFreeAsync(mround, stream);
+    if (cellinfo) (void)hipFreeAsync(cellinfo, stream);
+    if (qmem) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipFree(qmem);
+    }
+  }
+};
+
+// Fixed point with >= 8 one-hot features: the sparse form (sc.qa: the one-hot / multi-bin partition, uploaded,
+// and the rows' one-hot bit masks packed by gbdt_pack_bits).  0, or the allocation's error
+int build_quant_aux(const FitArgs& a, FitScratch& sc) {
+  if (!a.quant_bits) return 0;
+  const int F = a.F;
+  QuantAux& qa = sc.qa;
+  std::vector<int> bcell, bfeat, fmap;
+  qa.foffm_h.push_back(0);
+  for (int f = 0; f < F; ++f) {
+    const int nbins = a.foff_h[f + 1] - a.foff_h[f];
+    if (nbins == 2) {
+      bcell.push_back(a.foff_h[f]);
+      bfeat.push_back(f);
+    } else {
+      fmap.push_back(f);
+      qa.foffm_h.push_back(qa.foffm_h.back() + nbins);
+    }
+  }
+  // sparse form only when one node's cells fit the LDS budget (many continuous features: dense form)
+  if (bcell.size() < 8 ||
+      (int64_t)16 * (QB_REP * (((int)bcell.size() + 1) | 1) + qa.foffm_h.back()) > HIST_LDS_BUDGET)
+    return 0;
+  qa.nb = (int)bcell.size();
+  qa.WB = (qa.nb + 63) / 64;
+  qa.Fm = (int)fmap.size();
+  const size_t ints = 2 * (size_t)qa.nb + (size_t)qa.Fm + (size_t)qa.Fm + 1;
+  const size_t mask_off = (ints * 4 + 15) / 16 * 16;
+  if (hipError_t e = hipMalloc(&sc.qmem, mask_off + (size_t)a.n * qa.WB * 8)) return (int)e;
+  std::vector<int> hostv;  // [bcell | bfeat | fmap | foffm]
+  for (const auto* v : {&bcell, &bfeat, &fmap, &qa.foffm_h}) hostv.insert(hostv.end(), v->begin(), v->end());
+  int* dv = static_cast<int*>(sc.qmem);
+  (void)hipMemcpyAsync(dv, hostv.data(), hostv.size() * 4, hipMemcpyHostToDevice, a.stream);
+  qa.bcell_d = dv;
+  qa.fmap_d = dv + 2 * qa.nb;
+  qa.foffm_d = dv + 2 * qa.nb + qa.Fm;
+  qa.bmask_d = reinterpret_cast<const uint64_t*>(static_cast<char*>(sc.qmem) + mask_off);
+  hipLaunchKernelGGL(gbdt_pack_bits, dim3(grid_for((int64_t)a.n * qa.WB)), dim3(256), 0, a.stream, a.bins, a.n, F,
+                     dv + qa.nb, qa.nb, qa.WB, const_cast<uint64_t*>(qa.bmask_d));
+  return 0;
+}
+
+// Direct split candidates (gbdt_split): cell -> {feature, its first cell, its end cell} when no feature has
+// more than SPLIT_DIRECT_MAX_BINS bins (the reference's calendar features: 31)
+bool build_cellinfo(const FitArgs& a, int C, FitScratch& sc) {
+  const int* foff_h = a.foff_h;
+  int maxb = 0;
+  for (int f = 0; f < a.F; ++f) maxb = foff_h[f + 1] - foff_h[f] > maxb ? foff_h[f + 1] - foff_h[f] : maxb;
+  if (maxb > SPLIT_DIRECT_MAX_BINS || C <= 0) return true;
+  std::vector<int4> ci((size_t)C);
+  for (int f = 0; f < a.F; ++f)
+    for (int c = foff_h[f]; c < foff_h[f + 1]; ++c) ci[c] = int4{f, foff_h[f], foff_h[f + 1], 0};
+  const size_t bytes = ci.size() * sizeof(int4);
+  return hipMallocAsync(reinterpret_cast<void**>(&sc.cellinfo), bytes, a.stream) == hipSuccess &&
+         hipMemcpyAsync(sc.cellinfo, ci.data(), bytes, hipMemcpyHostToDevice, a.stream) == hipSuccess;
+}
+
+struct RoundView {  // the tree arrays of one round, addressed from the host
+  int round;
+  int8_t* st;
+  int16_t* fe;
+  uint8_t* sb;
+  float *lf, *gn, *cv;
+};
+// The only state carried from level to level and round to round (presplit): the previous level's split,
+// deferred into the next histogram pass, with its LDS size, and the arrivals per task so far in this call
+struct PreCarry {
+  HistPre pending;
+  size_t pending_lds = 0;
+  int cum = 0;
+};
+
+// round `rv.round`'s level-0 pass doing round - 1's update and the round's start
+HistUpdate level0_update(const FitArgs& a, const FitPlan& p, const FitScratch& sc, const RoundView& rv) {
+  HistUpdate hu;
+  hu.on = 1, hu.apply = rv.round > a.r0, hu.round = rv.round, hu.nz = 1, hu.NN = p.NN, hu.plevel = a.max_depth - 1;
+  hu.obj = a.obj, hu.metric = a.metric, hu.subsample = a.subsample, hu.seed = a.seed;
+  hu.margin = a.margin, hu.Y = a.Y, hu.g = a.g, hu.h = a.h, hu.node = a.node;
+  hu.st = rv.st, hu.fe = rv.fe, hu.sb = rv.sb, hu.gn = rv.gn;
+  if (hu.apply) {  // round - 1's tree, node ids and metric partials
+    const int64_t rp = (int64_t)(rv.round - 1) * a.T * p.NN;
+    hu.pst = a.status + rp, hu.pfe = a.feat + rp, hu.psb = a.sbin + rp, hu.plf = a.leaf + rp;
+    hu.pnode = (a.max_depth - 1) & 1 ? a.node2 : a.node;
+    hu.mpart = sc.mround + (int64_t)(rv.round - 1 - a.r0) * p.sets * p.mstride, hu.mstride = p.mstride;
+    hu.evs = eval_sets(a.evals, a.n_evals, a.T);
+  }
+  return hu;
+}
+// the prune / leaves by the last-arriving block of each task's last split (fused round)
+SplitFinal split_final(const FitArgs& a, const FitPlan& p, const RoundView& rv) {
+  return SplitFinal{p.tctr, rv.lf, rv.cv, a.gamma, (double)a.eta, a.max_depth};
+}
+// the root split inside the level-0 pass (HistSplit: its task's last-arriving chunk block)
+HistSplit root_split(const FitArgs& a, const FitPlan& p, const FitScratch& sc, const RoundView& rv) {
+  HistSplit hsp;
+  hsp.on = 1, hsp.ctr = p.tctr + a.T, hsp.NN = p.NN, hsp.cstride = (int64_t)a.T * p.C * 2;
+  hsp.G = a.Gs, hsp.H = a.Hs, hsp.lam = (double)a.lam, hsp.mcw = (double)a.mcw;
+  hsp.oneshot = 1, hsp.pscan = p.root.pscan, hsp.cellinfo = sc.cellinfo;
+  if (a.max_depth == 1) hsp.fin = split_final(a, p, rv);
+  return hsp;
+}
+
+// One level: the histogram pass (with whatever the plan folds into it) and the split launch, unless the pass
+// did the split (fsplit) or the next level's pass will (presplit: left in `pc`)
+int enqueue_level(const FitArgs& a, const FitPlan& p, const FitScratch& sc, const RoundView& rv, int level,
+                  PreCarry& pc) {
+  const int T = a.T, F = a.F, NN = p.NN, C = p.C, nodesL = 1 << level;
+  hipStream_t s = a.stream;
+  int16_t* nb[2] = {a.node, p.fuse ? a.node2 : a.node};
+  double* lpart = p.presplit ? a.partial + (level & 1) * p.half : a.partial;  // this level's partials
+  LevelHist lh{level, T, a.n, F, a.bins, a.g, a.h, a.node, a.foff_h, a.foff_d, lpart, p.half, false, p.qscale};
+  lh.qa = sc.qa.nb ? &sc.qa : nullptr;
+  if (p.fuse && level >= 1) {
+    lh.node = nb[(level - 1) & 1];
+    lh.partition = HistPartition{nb[level & 1], rv.st, rv.fe, rv.sb, NN};
+  }
+  const bool fsplit = p.fsplit && level == 0;
+  const HistUpdate hu = p.hist_update && level == 0 ? level0_update(a, p, sc, rv) : HistUpdate();
+  const HistSplit hsp = fsplit ? root_split(a, p, sc, rv) : HistSplit();
+  if (hu.on) lh.update = &hu;
+  if (hsp.on) lh.root_split = &hsp, lh.min_lds = p.root.bytes;
+  if (pc.pending.on) {
+    pc.pending.want = pc.cum += pc.pending.nodes;
+    lh.pre = &pc.pending, lh.min_lds = pc.pending_lds;
+  }
+  int nch = 1;
+  const int rc = launch_level_hist(lh, &nch, s);
+  pc.pending = HistPre();
+  if (rc) return rc;
+  if (fsplit) return 0;  // (split done by the pass itself)
+  const int sth = (F >= 256 || nch > 1) ? 256 : ((F + 63) / 64) * 64;
+  const int64_t cstride = (int64_t)T * nodesL * C * 2;
+  const bool last = p.fuse && level == a.max_depth - 1;
+  const SplitLds sl = split_lds(nch, C, NN, last);
+  if (p.presplit && level >= 1 && level + 1 < a.max_depth) {  // runs in the next level's histogram pass
+    HistPre& pre = pc.pending;
+    pre.on = 1, pre.nodes = nodesL, pre.level = level, pre.NN = NN;
+    pre.hist = lpart, pre.nchunks = nch, pre.cstride = cstride, pre.oneshot = sl.oneshot, pre.pscan = sl.pscan;
+    pre.ctr = sc.sctr, pre.err = p.perr;
+    pre.G = a.Gs, pre.H = a.Hs, pre.lam = (double)a.lam, pre.mcw = (double)a.mcw, pre.cellinfo = sc.cellinfo;
+    pre.st = rv.st, pre.fe = rv.fe, pre.sb = rv.sb, pre.gn = rv.gn;
+    pc.pending_lds = sl.bytes;
+    return 0;
+  }
+  const SplitFinal fin = last ? split_final(a, p, rv) : SplitFinal();
+  if (a.quant_bits)
+    hipLaunchKernelGGL(gbdt_split<long long>, dim3(T * nodesL), dim3(sth), sl.bytes, s,
+                       reinterpret_cast<const long long*>(lpart), nch, cstride, a.foff_d, T, F, C, level, NN, a.Gs,
+                       a.Hs, rv.st, rv.fe, rv.sb, rv.gn, (double)a.lam, (double)a.mcw, p.qinv, fin, sl.oneshot,
+                       sl.pscan, sc.cellinfo);
+  else
+    hipLaunchKernelGGL(gbdt_split<double>, dim3(T * nodesL), dim3(sth), sl.bytes, s, lpart, nch, cstride, a.foff_d,
+                       T, F, C, level, NN, a.Gs, a.Hs, rv.st, rv.fe, rv.sb, rv.gn, (double)a.lam, (double)a.mcw, 0.0,
+                       fin, sl.oneshot, sl.pscan, sc.cellinfo);
+  if (!p.fuse)
+    hipLaunchKernelGGL(gbdt_partition, dim3(grid_for(p.TN)), dim3(256), 0, s, a.bins, a.node, T, a.n, F, NN, rv.st,
+                       rv.fe, rv.sb, level);
+  return 0;
+}
+
+// The round's update and its metrics (train + evals) into hist_out[round].  Elementwise metrics: the leaf
+// update / eval prediction, the metric partials and the final sum are one launch each (last-arriving block)
+int enqueue_round_metrics(const FitArgs& a, const FitPlan& p, const FitScratch& sc, const RoundView& rv) {
+  const int T = a.T, n = a.n, F = a.F, NN = p.NN, round = rv.round;
+  const int64_t TN = p.TN;
+  hipStream_t s = a.stream;
+  float* ho = a.hist_out + (int64_t)round * p.sets;
+  const int mb_train = grid_for(TN);
+  const bool fused_metric = a.metric < MET_MLOGLOSS;
+  if (fused_metric) {
+    NextRound nx;
+    if (p.next_in_update && round + 1 < a.r1) {
+      const int64_t tn = (int64_t)T * NN;
+      nx.round = round + 1, nx.subsample = a.subsample, nx.seed = a.seed;
+      nx.g = a.g, nx.h = a.h, nx.node = a.node;
+      nx.st = rv.st + tn, nx.fe = rv.fe + tn, nx.sb = rv.sb + tn, nx.gn = rv.gn + tn;
+    }
+    // the eval sets' predictions ride in the same launch (trailing blocks)
+    EvalSets evs;
+    int grid = mb_train;
+    if (a.n_evals <= 4) {
+      evs = eval_sets(a.evals, a.n_evals, T, &grid);
+      if (p.deferred) evs.pstride = p.mstride;
+    }
+    double* mp = p.deferred ? sc.mround + (int64_t)(round - a.r0) * p.sets * p.mstride : a.mpart;
+    hipLaunchKernelGGL(gbdt_update_metric, dim3(grid), dim3(256), 0, s, a.margin,
+                       p.fuse && ((a.max_depth - 1) & 1) ? a.node2 : a.node, T, n, NN, rv.st, rv.lf, a.Y, a.obj,
+                       a.metric, mp, p.deferred ? nullptr : p.mctr, ho, a.bins, F, p.fuse ? a.max_depth - 1 : -1,
+                       rv.fe, rv.sb, nx, mb_train, evs);
+    if (evs.count == a.n_evals) return launch_status();
+  } else {  // (a multi-class metric: a mean over the rows)
+    hipLaunchKernelGGL(gbdt_update, dim3(grid_for(TN)), dim3(256), 0, s, a.margin, a.node, T, n, NN, rv.st, rv.lf);
+    hipLaunchKernelGGL(gbdt_metric, dim3(mb_train), dim3(256), 0, s, a.margin, a.Y, T, n, a.obj, a.metric, a.mpart);
+    hipLaunchKernelGGL(gbdt_metric_final, dim3(1), dim3(256), 0, s, a.mpart, mb_train, (int64_t)n, a.metric, ho);
+  }
+  for (int e = 0; e < a.n_evals; ++e) {
+    const EmGbdtEval& ev = a.evals[e];
+    const int k0 = round * T, mb = grid_for((int64_t)T * ev.n);
+    if (fused_metric) {
+      hipLaunchKernelGGL(gbdt_predict_metric, dim3(mb), dim3(256), 0, s, ev.bins, ev.margin, T, ev.n, F, NN, k0,
+                         k0 + T, a.status, a.feat, a.sbin, a.leaf, ev.Y, a.obj, a.metric, a.mpart, p.mctr,
+                         ho + 1 + e);
+      continue;
+    }
+    hipLaunchKernelGGL(gbdt_predict, dim3(mb), dim3(256), 0, s, ev.bins, ev.margin, T, ev.n, F, NN, k0, k0 + T,
+                       a.status, a.feat, a.sbin, a.leaf);
+    hipLaunchKernelGGL(gbdt_metric, dim3(mb), dim3(256), 0, s, ev.margin, ev.Y, T, ev.n, a.obj, a.metric, a.mpart);
+    hipLaunchKernelGGL(gbdt_metric_final, dim3(1), dim3(256), 0, s, a.mpart, mb, (int64_t)ev.n, a.metric, ho + 1 + e);
+  }
+  return launch_status();
+}
+
+// One round's kernel sequence
+int enqueue_round(const FitArgs& a, const FitPlan& p, const FitScratch& sc, int round, PreCarry& pc) {
+  const int T = a.T, NN = p.NN;
+  const int64_t ro = (int64_t)round * T * NN;
+  const RoundView rv{round, a.status + ro, a.feat + ro, a.sbin + ro, a.leaf + ro, a.gainv + ro, a.cover + ro};
+  hipStream_t s = a.stream;
+  if (!p.hist_update && (!p.next_in_update || round == a.r0))
+    hipLaunchKernelGGL(gbdt_round_start, dim3(grid_for(p.TN > (int64_t)T * NN ? p.TN : (int64_t)T * NN)), dim3(256),
+                       0, s, rv.st, rv.fe, rv.sb, rv.gn, T * NN, NN, a.margin, a.Y, a.g, a.h, a.node, T, a.n, a.obj,
+                       a.subsample, a.seed, round);
+  for (int level = 0; level < a.max_depth; ++level)
+    if (int rc = enqueue_level(a, p, sc, rv, level, pc)) return rc;
+  if (!p.fuse)
+    hipLaunchKernelGGL(gbdt_finalize, dim3((T + 63) / 64), dim3(64), 0, s, T, NN, a.max_depth, rv.st, rv.fe, rv.gn,
+                       a.Gs, a.Hs, rv.lf, rv.cv, (double)a.lam, a.gamma, (double)a.eta);
+  // (hist_update: the round's update runs in the next round's level-0 pass, the call's last round's here)
+  return p.hist_update && round < a.r1 - 1 ? launch_status() : enqueue_round_metrics(a, p, sc, rv);
+}
+}  // namespace
+
 // Trains rounds [r0, r1).  Tree arrays hold ALL rounds: [R*T][NN] (tree k = round*T + task).
 // foff_h / foff_d: feature -> first compact histogram cell, [F+1] (host copy for the plan, device copy
 // for the kernels); feature f has foff[f+1]-foff[f] bins.
 // scratch: g, h [T][n]; node, node2 int16 [T][n]; partial (em_gbdt_partial_doubles); G, H [T][NN]; mpart double[5 * 4096]
 // hist_out: float [R][1 + n_evals] (metric of train + each eval set after each round)
+// launch_flags: EM_GBDT_SEPARATE, EM_GBDT_PRESPLIT (the only switches of the round form: FitPlan)
 EM_API int em_gbdt_fit(const uint8_t* bins, const float* Y, int n, int F, const int* foff_h, const int* foff_d, int T,
                        float* margin, const EmGbdtEval* evals, int n_evals, int r0, int r1, int max_depth, int obj,
                        int metric, float eta, float lam, float gamma, float mcw, float subsample, uint32_t seed,
@@ -1858,402 +2224,39 @@ EM_API int em_gbdt_fit(const uint8_t* bins, const float* Y, int n, int F, const 
   // fixed-point histograms (quant_bits = s > 0): the caller guarantees |g|, |h| <= 1 and n < 2^(61-s),
   // so every per-cell and per-node sum of q = rint(x * 2^s) stays below 2^61 in magnitude
   if (quant_bits && (obj == OBJ_SQERR || (int64_t)n >= (1ll << (61 - quant_bits)))) return EM_ERR_ARG;
-  const double qscale = quant_bits ? ldexp(1.0, quant_bits) : 0.0, qinv = quant_bits ? ldexp(1.0, -quant_bits) : 0.0;
-  const int NN = (1 << (max_depth + 1)) - 1;
-  const int C = foff_h[F];
-  const int64_t TN = (int64_t)T * n;
-  int* mctr = metric_counter();  // arrival counter of the fused metric launches (re-armed by each)
-  if (!mctr) return EM_ERR_ARG;
-  // fixed point with >= 8 one-hot features: the sparse form (QuantAux)
-  QuantAux qa;
-  void* qmem = nullptr;
-  if (quant_bits) {
-    std::vector<int> bcell, bfeat, fmap;
-    qa.foffm_h.push_back(0);
-    for (int f = 0; f < F; ++f) {
-      const int nbins = foff_h[f + 1] - foff_h[f];
-      if (nbins == 2) {
-        bcell.push_back(foff_h[f]);
-        bfeat.push_back(f);
-      } else {
-        fmap.push_back(f);
-        qa.foffm_h.push_back(qa.foffm_h.back() + nbins);
-      }
-    }
-    // sparse form only when one node's cells fit the LDS budget (many continuous features: dense form)
-    if (bcell.size() >= 8 && (int64_t)16 * (QB_REP * (((int)bcell.size() + 1) | 1) + qa.foffm_h.back()) <=
-                                 HIST_LDS_BUDGET) {
-      qa.nb = (int)bcell.size();
-      qa.WB = (qa.nb + 63) / 64;
-      qa.Fm = (int)fmap.size();
-      const size_t ints = 2 * (size_t)qa.nb + (size_t)qa.Fm + (size_t)qa.Fm + 1;
-      const size_t mask_off = (ints * 4 + 15) / 16 * 16;
-      if (hipError_t e = hipMalloc(&qmem, mask_off + (size_t)n * qa.WB * 8)) return (int)e;
-      std::vector<int> hostv;
-      hostv.insert(hostv.end(), bcell.begin(), bcell.end());
-      hostv.insert(hostv.end(), bfeat.begin(), bfeat.end());
-      hostv.insert(hostv.end(), fmap.begin(), fmap.end());
-      hostv.insert(hostv.end(), qa.foffm_h.begin(), qa.foffm_h.end());
-      int* dv = static_cast<int*>(qmem);
-      (void)hipMemcpyAsync(dv, hostv.data(), hostv.size() * 4, hipMemcpyHostToDevice, stream);
-      qa.bcell_d = dv;
-      qa.fmap_d = dv + 2 * qa.nb;
-      qa.foffm_d = dv + 2 * qa.nb + qa.Fm;
-      qa.bmask_d = reinterpret_cast<const uint64_t*>(static_cast<char*>(qmem) + mask_off);
-      hipLaunchKernelGGL(gbdt_pack_bits, dim3(grid_for((int64_t)n * qa.WB)), dim3(256), 0, stream, bins, n, F,
-                         dv + qa.nb, qa.nb, qa.WB, const_cast<uint64_t*>(qa.bmask_d));
-    }
-  }
-  struct Free {  // the scratch outlives every launch of this call: freed after the stream drains
-    void* p;
-    hipStream_t s;
-    ~Free() {
-      if (p) {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(p);
-      }
-    }
-  } qfree{qmem, stream};
-  // direct split candidates (gbdt_split): cell -> {feature, its first cell, its end cell} when no feature
-  // has more than SPLIT_DIRECT_MAX_BINS bins (the reference's calendar features: 31); stream-ordered
-  // allocation, freed after the last round's launches
-  int4* cellinfo_d = nullptr;
-  {
-    int maxb = 0;
-    for (int f = 0; f < F; ++f) maxb = foff_h[f + 1] - foff_h[f] > maxb ? foff_h[f + 1] - foff_h[f] : maxb;
-    if (maxb <= SPLIT_DIRECT_MAX_BINS && C > 0) {
-      std::vector<int4> ci((size_t)C);
-      for (int f = 0; f < F; ++f)
-        for (int c = foff_h[f]; c < foff_h[f + 1]; ++c) ci[c] = int4{f, foff_h[f], foff_h[f + 1], 0};
-      if (hipMallocAsync(reinterpret_cast<void**>(&cellinfo_d), ci.size() * sizeof(int4), stream) != hipSuccess ||
-          hipMemcpyAsync(cellinfo_d, ci.data(), ci.size() * sizeof(int4), hipMemcpyHostToDevice, stream) != hipSuccess)
-        return EM_ERR_ARG;
-    }
-  }
-  struct FreeAsync {
-    void* p;
-    hipStream_t s;
-    ~FreeAsync() {
-      if (p) (void)hipFreeAsync(p, s);
-    }
-  } cfree{cellinfo_d, stream};
-  // Exact-form fits with an elementwise metric run the fused round: the previous level's partition
-  // inside each histogram pass (double-buffered nodes), the prune / leaves in the last level's split
-  // (last-arriving block per task), the last partition in the update, and -- per-task objectives --
-  // the next round's start in the update too: 7 launches per depth-3 round instead of 13.
-  // Bit-identical to the separate launches (same arithmetic on the same values).
-  // launch_flags & EM_GBDT_SEPARATE: the separate launches (the bit-identity tests; quantised fits and
-  // multi-class metrics always take them)
-  int* tctr = nullptr;
-  const bool fuse = !(launch_flags & EM_GBDT_SEPARATE) && !quant_bits && metric < MET_MLOGLOSS &&
-                    max_depth <= SPLIT_FINAL_MAX_DEPTH && node2 && (tctr = task_counters(2 * T)) != nullptr;
-  // deferred metrics (metric_arrive_final with ctr == nullptr): every round's per-block partials of the
-  // train and eval sets, reduced by gbdt_metric_rounds after the last round
-  const int sets = 1 + n_evals;
-  const bool deferred = metric < MET_MLOGLOSS && n_evals <= 4;
-  int64_t mstride = grid_for(TN);
-  for (int e = 0; e < n_evals; ++e)
-    mstride = grid_for((int64_t)T * evals[e].n) > mstride ? grid_for((int64_t)T * evals[e].n) : mstride;
-  // update-in-histogram rounds (HistUpdate): the level-0 histogram pass of round r does round r - 1's
-  // update; one update launch for the call's last round
-  HistPlan p0;
-  const bool hist_update = fuse && obj != OBJ_SOFTMAX && deferred && plan_hist(0, n, T, F, foff_h, false, p0) &&
-                           p0.nft * p0.ntn == 1 && p0.nchunks * (int64_t)T <= (int64_t)1 << 20;
-  const int nch0 = hist_update ? p0.nchunks : 0;
-  if (hist_update && (int64_t)T * nch0 > mstride) mstride = (int64_t)T * nch0;
-  double* mround = nullptr;
-  if (deferred && hipMallocAsync(reinterpret_cast<void**>(&mround), (size_t)(r1 - r0) * sets * mstride * sizeof(double),
-                                 stream) != hipSuccess)
+  const FitArgs a{bins, Y, n, F, foff_h, foff_d, T, margin, evals, n_evals, r0, r1, max_depth, obj, metric, eta, lam,
+                  gamma, mcw, subsample, seed, g, h, node, node2, partial, partial_doubles, Gs, Hs, mpart, status,
+                  feat, sbin, leaf, gainv, cover, hist_out, quant_bits, launch_flags, stream};
+  FitPlan p;
+  if (!make_plan(a, p)) return EM_ERR_ARG;
+  FitScratch sc(stream);
+  if (int rc = build_quant_aux(a, sc)) return rc;
+  if (!build_cellinfo(a, p.C, sc)) return EM_ERR_ARG;
+  if (p.deferred && hipMallocAsync(reinterpret_cast<void**>(&sc.mround),
+                                   (size_t)(r1 - r0) * p.sets * p.mstride * sizeof(double), stream) != hipSuccess)
     return EM_ERR_ARG;
-  FreeAsync mfree{mround, stream};
-  // EM_GBDT_PRESPLIT=1: levels >= 1 of the exact fused round run level L's split in the leading blocks of
-  // level L + 1's histogram pass (HistPre) when the partial buffer holds two levels' partials (double-
-  // buffered halves).  Bit-identical trees; measured equal on the reference fit (849-855 k vs 844-853 k
-  // trees/s, 3 interleaved rounds, profiles/r6/gbdt_presplit_ab.txt): the launch boundary it removes is
-  // paid back as the in-launch hand-off, so the split launches stay the default
-  int64_t pneed = 0;
-  for (int l = 0; l < max_depth; ++l) {
-    const int64_t v = partial_need(l, n, T, F, foff_h);
-    pneed = v > pneed ? v : pneed;
-  }
-  static const bool presplit_env = [] {
-    const char* e = std::getenv("EM_GBDT_PRESPLIT");
-    return e && e[0] == '1';
-  }();
-  const bool presplit = (presplit_env || (launch_flags & EM_GBDT_PRESPLIT)) && fuse && max_depth >= 3 && pneed > 0 &&
-                        partial_doubles >= 2 * pneed;
-  const int64_t half = presplit ? (partial_doubles / 2) & ~(int64_t)1 : partial_doubles;
-  int* sctr = nullptr;  // [T] cumulative split arrivals of this fit
-  if (presplit) {
-    if (hipMallocAsync(reinterpret_cast<void**>(&sctr), (size_t)T * sizeof(int), stream) != hipSuccess ||
-        hipMemsetAsync(sctr, 0, (size_t)T * sizeof(int), stream) != hipSuccess)
-      return EM_ERR_ARG;
-  }
-  FreeAsync sfree{sctr, stream};
-  int* perr = presplit ? fused_error_word() : nullptr;
-  if (presplit && !perr) return EM_ERR_ARG;
-  int pre_cum = 0;  // arrivals per task so far
-  // one round's kernel sequence (the arrays of `round` addressed from the host)
-  auto enqueue_round = [&](int round, hipStream_t s) -> int {
-    const int64_t ro = (int64_t)round * T * NN;
-    int8_t* st = status + ro;
-    int16_t* fe = feat + ro;
-    uint8_t* sb = sbin + ro;
-    float* lf = leaf + ro;
-    float* gn = gainv + ro;
-    float* cv = cover + ro;
-    const bool next_in_update = fuse && obj != OBJ_SOFTMAX && !hist_update;  // round + 1 started by this update
-    int16_t* nb[2] = {node, fuse ? node2 : node};
-    HistPre pending;  // the previous level's split, deferred into this level's histogram pass
-    size_t pending_lds = 0;
-    if (!hist_update && (!next_in_update || round == r0))
-      hipLaunchKernelGGL(gbdt_round_start, dim3(grid_for(TN > (int64_t)T * NN ? TN : (int64_t)T * NN)), dim3(256), 0,
-                         s, st, fe, sb, gn, T * NN, NN, margin, Y, g, h, node, T, n, obj, subsample, seed, round);
-    for (int level = 0; level < max_depth; ++level) {
-      const int nodesL = 1 << level;
-      int nch = 1;
-      HistPartition hp;
-      const int16_t* nin = node;
-      if (fuse && level >= 1) {
-        nin = nb[(level - 1) & 1];
-        hp.node_out = nb[level & 1];
-        hp.st = st;
-        hp.fe = fe;
-        hp.sb = sb;
-        hp.NN = NN;
-      }
-      HistUpdate hu;
-      if (hist_update && level == 0) {
-        hu.on = 1;
-        hu.apply = round > r0;
-        hu.round = round;
-        hu.obj = obj;
-        hu.metric = metric;
-        hu.NN = NN;
-        hu.plevel = max_depth - 1;
-        hu.nz = 1;
-        hu.subsample = subsample;
-        hu.seed = seed;
-        hu.margin = margin;
-        hu.Y = Y;
-        hu.g = g;
-        hu.h = h;
-        hu.node = node;
-        hu.st = st;
-        hu.fe = fe;
-        hu.sb = sb;
-        hu.gn = gn;
-        if (hu.apply) {  // round - 1's tree, node ids and metric partials
-          const int64_t rp = ro - (int64_t)T * NN;
-          hu.pst = status + rp;
-          hu.pfe = feat + rp;
-          hu.psb = sbin + rp;
-          hu.plf = leaf + rp;
-          hu.pnode = nb[(max_depth - 1) & 1];
-          hu.mpart = mround + (int64_t)(round - 1 - r0) * sets * mstride;
-          hu.mstride = mstride;
-          for (int e = 0; e < n_evals; ++e) {
-            hu.evs.bins[e] = evals[e].bins;
-            hu.evs.margin[e] = evals[e].margin;
-            hu.evs.Y[e] = evals[e].Y;
-            hu.evs.n[e] = evals[e].n;
-          }
-          hu.evs.count = n_evals;
-        }
-      }
-      // the root split inside the level-0 pass (HistSplit: its task's last-arriving chunk block)
-      HistSplit hsp;
-      size_t hsp_lds = 0;
-      const bool fsplit = hist_update && level == 0 && nch0 > 1 && nch0 <= SPLIT_FOLD_MAX_CHUNKS &&
-                          (int64_t)C * 16 <= SPLIT_FOLD_MAX_LDS && (int64_t)nch0 * C * 16 <= SPLIT_ONESHOT_LDS;
-      if (fsplit) {
-        hsp.on = 1;
-        hsp.ctr = tctr + T;
-        hsp.G = Gs;
-        hsp.H = Hs;
-        hsp.lam = (double)lam;
-        hsp.mcw = (double)mcw;
-        hsp.NN = NN;
-        hsp.cstride = (int64_t)T * C * 2;
-        hsp.oneshot = 1;
-        hsp.cellinfo = cellinfo_d;
-        size_t sl = ((size_t)nch0 * C * 16 + 15) & ~(size_t)15;
-        const size_t sb_ = ((size_t)C * 20 + 15) & ~(size_t)15;
-        hsp.pscan = sl + sb_ + (size_t)NN * 24 <= 60 * 1024;
-        if (hsp.pscan) sl += sb_;
-        if (max_depth == 1) {
-          hsp.fin.tctr = tctr;
-          hsp.fin.leaf = lf;
-          hsp.fin.cover = cv;
-          hsp.fin.gamma = gamma;
-          hsp.fin.eta = (double)eta;
-          hsp.fin.max_depth = max_depth;
-          sl += (size_t)NN * 24;
-        }
-        hsp_lds = sl;
-      }
-      double* lpart = presplit ? partial + (level & 1) * half : partial;  // this level's partials
-      HistPre* prep = nullptr;
-      if (pending.on) {
-        pre_cum += pending.nodes;
-        pending.want = pre_cum;
-        prep = &pending;
-      }
-      const int rc = launch_level_hist(level, bins, g, h, nin, T, n, F, foff_h, foff_d, lpart, half,
-                                       false, qscale, &nch, s, qa.nb ? &qa : nullptr, hp,
-                                       hist_update && level == 0 ? &hu : nullptr, fsplit ? &hsp : nullptr,
-                                       prep ? pending_lds : hsp_lds, prep);
-      pending = HistPre();
-      if (rc) return rc;
-      if (fsplit) continue;  // (split done by the pass itself)
-      const int sth = (F >= 256 || nch > 1) ? 256 : ((F + 63) / 64) * 64;
-      const int64_t cstride = (int64_t)T * nodesL * C * 2;
-      const int oneshot = nch > 1 && (int64_t)nch * C * 16 <= SPLIT_ONESHOT_LDS;
-      size_t slds = nch > 1 ? (((size_t)(oneshot ? nch : 1) * C * 16 + 15) & ~(size_t)15) : 0;
-      const size_t scan_b = ((size_t)C * 20 + 15) & ~(size_t)15;
-      const int pscan = slds + scan_b + (size_t)NN * 24 <= 60 * 1024;  // (+ the finalize area: < 64 KB)
-      if (pscan) slds += scan_b;
-      SplitFinal fin;
-      if (fuse && level == max_depth - 1) {
-        fin.tctr = tctr;
-        fin.leaf = lf;
-        fin.cover = cv;
-        fin.gamma = gamma;
-        fin.eta = (double)eta;
-        fin.max_depth = max_depth;
-        slds += (size_t)NN * 24;
-      }
-      if (presplit && level >= 1 && level + 1 < max_depth) {  // runs in the next level's histogram pass
-        pending.on = 1;
-        pending.nodes = nodesL;
-        pending.level = level;
-        pending.nchunks = nch;
-        pending.oneshot = oneshot;
-        pending.pscan = pscan;
-        pending.NN = NN;
-        pending.ctr = sctr;
-        pending.err = perr;
-        pending.hist = lpart;
-        pending.cstride = cstride;
-        pending.G = Gs;
-        pending.H = Hs;
-        pending.st = st;
-        pending.fe = fe;
-        pending.sb = sb;
-        pending.gn = gn;
-        pending.lam = (double)lam;
-        pending.mcw = (double)mcw;
-        pending.cellinfo = cellinfo_d;
-        pending_lds = slds;
-        continue;
-      }
-      if (quant_bits)
-        hipLaunchKernelGGL(gbdt_split<long long>, dim3(T * nodesL), dim3(sth), slds, s,
-                           reinterpret_cast<const long long*>(lpart), nch, cstride, foff_d, T, F, C, level, NN, Gs,
-                           Hs, st, fe, sb, gn, (double)lam, (double)mcw, qinv, fin, oneshot, pscan, cellinfo_d);
-      else
-        hipLaunchKernelGGL(gbdt_split<double>, dim3(T * nodesL), dim3(sth), slds, s, lpart, nch, cstride,
-                           foff_d, T, F, C, level, NN, Gs, Hs, st, fe, sb, gn, (double)lam, (double)mcw, 0.0, fin,
-                           oneshot, pscan, cellinfo_d);
-      if (!fuse)
-        hipLaunchKernelGGL(gbdt_partition, dim3(grid_for(TN)), dim3(256), 0, s, bins, node, T, n, F, NN, st, fe, sb,
-                           level);
-    }
-    if (!fuse)
-      hipLaunchKernelGGL(gbdt_finalize, dim3((T + 63) / 64), dim3(64), 0, s, T, NN, max_depth, st, fe, gn, Gs, Hs, lf,
-                         cv, (double)lam, gamma, (double)eta);
-    if (hist_update && round < r1 - 1) {  // this round's update runs in the next round's level-0 pass
-      EM_CHECK_LAUNCH();
-      return 0;
-    }
-    // metrics (train + evals) into hist_out[round].  Elementwise metrics: the leaf update / eval
-    // prediction, the metric partials and the final sum are one launch each (last-arriving block)
-    const int hs = 1 + n_evals;
-    float* ho = hist_out + (int64_t)round * hs;
-    const int mb_train = grid_for(TN);
-    const bool fused_metric = metric < MET_MLOGLOSS;
-    if (fused_metric) {
-      NextRound nx;
-      if (next_in_update && round + 1 < r1) {
-        const int64_t rn = ro + (int64_t)T * NN;
-        nx.round = round + 1;
-        nx.g = g;
-        nx.h = h;
-        nx.node = node;
-        nx.st = st + (int64_t)T * NN;
-        nx.fe = fe + (int64_t)T * NN;
-        nx.sb = sb + (int64_t)T * NN;
-        nx.gn = gainv + rn;
-        nx.subsample = subsample;
-        nx.seed = seed;
-      }
-      // the eval sets' predictions ride in the same launch (trailing blocks)
-      EvalSets evs;
-      int grid = mb_train;
-      if (n_evals <= 4) {
-        for (int e = 0; e < n_evals; ++e) {
-          evs.bins[e] = evals[e].bins;
-          evs.margin[e] = evals[e].margin;
-          evs.Y[e] = evals[e].Y;
-          evs.n[e] = evals[e].n;
-          evs.mb[e] = grid_for((int64_t)T * evals[e].n);
-          grid += evs.mb[e];
-        }
-        evs.count = n_evals;
-        if (deferred) evs.pstride = mstride;
-      }
-      double* mp = deferred ? mround + (int64_t)(round - r0) * sets * mstride : mpart;
-      hipLaunchKernelGGL(gbdt_update_metric, dim3(grid), dim3(256), 0, s, margin,
-                         fuse ? nb[(max_depth - 1) & 1] : node, T, n, NN, st, lf, Y, obj, metric, mp,
-                         deferred ? nullptr : mctr, ho,
-                         bins, F, fuse ? max_depth - 1 : -1, fe, sb, nx, mb_train, evs);
-      if (evs.count == n_evals) {
-        EM_CHECK_LAUNCH();
-        return 0;
-      }
-    } else {
-      hipLaunchKernelGGL(gbdt_update, dim3(grid_for(TN)), dim3(256), 0, s, margin, node, T, n, NN, st, lf);
-      hipLaunchKernelGGL(gbdt_metric, dim3(mb_train), dim3(256), 0, s, margin, Y, T, n, obj, metric, mpart);
-      hipLaunchKernelGGL(gbdt_metric_final, dim3(1), dim3(256), 0, s, mpart, mb_train,
-                         metric >= MET_MLOGLOSS ? (int64_t)n : TN, metric, ho);
-    }
-    for (int e = 0; e < n_evals; ++e) {
-      const int64_t TE = (int64_t)T * evals[e].n;
-      const int k0 = round * T;
-      const int mb = grid_for(TE);
-      if (fused_metric) {
-        hipLaunchKernelGGL(gbdt_predict_metric, dim3(mb), dim3(256), 0, s, evals[e].bins, evals[e].margin, T,
-                           evals[e].n, F, NN, k0, k0 + T, status, feat, sbin, leaf, evals[e].Y, obj, metric, mpart,
-                           mctr, ho + 1 + e);
-        continue;
-      }
-      hipLaunchKernelGGL(gbdt_predict, dim3(grid_for(TE)), dim3(256), 0, s, evals[e].bins, evals[e].margin, T,
-                         evals[e].n, F, NN, k0, k0 + T, status, feat, sbin, leaf);
-      hipLaunchKernelGGL(gbdt_metric, dim3(mb), dim3(256), 0, s, evals[e].margin, evals[e].Y, T, evals[e].n, obj,
-                         metric, mpart);
-      hipLaunchKernelGGL(gbdt_metric_final, dim3(1), dim3(256), 0, s, mpart, mb,
-                         metric >= MET_MLOGLOSS ? (int64_t)evals[e].n : TE, metric, ho + 1 + e);
-    }
-    EM_CHECK_LAUNCH();
-    return 0;
-  };
+  const size_t tb = (size_t)T * sizeof(int);
+  if (p.presplit && (hipMallocAsync(reinterpret_cast<void**>(&sc.sctr), tb, stream) != hipSuccess ||
+                     hipMemsetAsync(sc.sctr, 0, tb, stream) != hipSuccess))
+    return EM_ERR_ARG;
+  PreCarry pc;
   for (int round = r0; round < r1; ++round)
-    if (int rc = enqueue_round(round, stream)) return rc;
-  if (deferred) {
+    if (int rc = enqueue_round(a, p, sc, round, pc)) return rc;
+  if (p.deferred) {  // every round's metric partials -> hist_out
     MetricRounds mr{};
-    mr.count[0] = TN;
+    mr.count[0] = p.TN;
     for (int e = 0; e < n_evals; ++e) mr.count[1 + e] = (int64_t)T * evals[e].n;
-    const int first = hist_update ? r1 - 1 : r0;  // rounds [r0, first): partials of the level-0 passes
+    const int first = p.hist_update ? r1 - 1 : r0;  // rounds [r0, first): partials of the level-0 passes
     if (first > r0) {
-      for (int k = 0; k < sets; ++k) mr.nb[k] = T * nch0;
-      hipLaunchKernelGGL(gbdt_metric_rounds, dim3((first - r0) * sets), dim3(256), 0, stream, mround, mstride, sets,
-                         mr, metric, hist_out + (int64_t)r0 * sets);
+      for (int k = 0; k < p.sets; ++k) mr.nb[k] = T * p.nch0;
+      hipLaunchKernelGGL(gbdt_metric_rounds, dim3((first - r0) * p.sets), dim3(256), 0, stream, sc.mround, p.mstride,
+                         p.sets, mr, metric, hist_out + (int64_t)r0 * p.sets);
     }
-    mr.nb[0] = grid_for(TN);
+    mr.nb[0] = grid_for(p.TN);
     for (int e = 0; e < n_evals; ++e) mr.nb[1 + e] = grid_for((int64_t)T * evals[e].n);
-    hipLaunchKernelGGL(gbdt_metric_rounds, dim3((r1 - first) * sets), dim3(256), 0, stream,
-                       mround + (int64_t)(first - r0) * sets * mstride, mstride, sets, mr, metric,
-                       hist_out + (int64_t)first * sets);
+    hipLaunchKernelGGL(gbdt_metric_rounds, dim3((r1 - first) * p.sets), dim3(256), 0, stream,
+                       sc.mround + (int64_t)(first - r0) * p.sets * p.mstride, p.mstride, p.sets, mr, metric,
+                       hist_out + (int64_t)first * p.sets);
     EM_CHECK_LAUNCH();
   }
   return 0;
@@ -2285,8 +2288,7 @@ EM_API int em_gbdt_stamps(unsigned long long* out) {
 EM_API int em_gbdt_init_margin(float* margin, int64_t total, float base, hipStream_t stream) {
   if (!margin || total < 0) return EM_ERR_ARG;
   hipLaunchKernelGGL(gbdt_init_margin, dim3(grid_for(total)), dim3(256), 0, stream, margin, total, base);
-  EM_CHECK_LAUNCH();
-  return 0;
+  return launch_status();
 }
 
 EM_API int em_gbdt_predict(const uint8_t* bins, float* margin, int T, int n, int F, int max_depth, int k0, int k1,
@@ -2297,8 +2299,7 @@ EM_API int em_gbdt_predict(const uint8_t* bins, float* margin, int T, int n, int
   const int NN = (1 << (max_depth + 1)) - 1;
   hipLaunchKernelGGL(gbdt_predict, dim3(grid_for((int64_t)T * n)), dim3(256), 0, stream, bins, margin, T, n, F, NN, k0,
                      k1, status, feat, sbin, leaf);
-  EM_CHECK_LAUNCH();
-  return 0;
+  return launch_status();
 }
 
 // ---------------------------------------------------------------- data-parallel (C4) primitives
@@ -2316,8 +2317,7 @@ EM_API int em_gbdt_dp_round_begin(int round, int T, int n, int max_depth, const 
                      T * NN, NN);
   hipLaunchKernelGGL(gbdt_grad, dim3(grid_for(TN)), dim3(256), 0, stream, margin, Y, g, h, node, T, n, obj, subsample,
                      seed, round);
-  EM_CHECK_LAUNCH();
-  return 0;
+  return launch_status();
 }
 
 // histogram of one level folded into partial[0 : T*2^level*C*2]; returns that length in *len_out
@@ -2328,8 +2328,8 @@ EM_API int em_gbdt_dp_level_hist(int level, const uint8_t* bins, const float* g,
       !foff_d)
     return EM_ERR_ARG;
   int nch = 1;
-  const int rc = launch_level_hist(level, bins, g, h, node, T, n, F, foff_h, foff_d, partial, partial_doubles, true,
-                                   0.0, &nch, stream);
+  const LevelHist lh{level, T, n, F, bins, g, h, node, foff_h, foff_d, partial, partial_doubles, true, 0.0};
+  const int rc = launch_level_hist(lh, &nch, stream);
   if (rc) return rc;
   EM_CHECK_LAUNCH();
   *len_out = (int64_t)T * (1 << level) * foff_h[F] * 2;
@@ -2351,8 +2351,7 @@ EM_API int em_gbdt_dp_level_split(int level, const uint8_t* bins, const double* 
                      (const int4*)nullptr);
   hipLaunchKernelGGL(gbdt_partition, dim3(grid_for(TN)), dim3(256), 0, stream, bins, node, T, n, F, NN, status, feat,
                      sbin, level);
-  EM_CHECK_LAUNCH();
-  return 0;
+  return launch_status();
 }
 
 EM_API int em_gbdt_dp_round_end(int T, int n, int max_depth, float* margin, const int16_t* node, int8_t* status,
@@ -2364,8 +2363,7 @@ EM_API int em_gbdt_dp_round_end(int T, int n, int max_depth, float* margin, cons
   hipLaunchKernelGGL(gbdt_finalize, dim3((T + 63) / 64), dim3(64), 0, stream, T, NN, max_depth, status, feat, gainv,
                      Gs, Hs, leaf, cover, (double)lam, gamma, (double)eta);
   hipLaunchKernelGGL(gbdt_update, dim3(grid_for(TN)), dim3(256), 0, stream, margin, node, T, n, NN, status, leaf);
-  EM_CHECK_LAUNCH();
-  return 0;
+  return launch_status();
 }
 
 // sum (not mean) of the per-element metric term over [T][n] margins -> out[0] (double)
@@ -2380,6 +2378,5 @@ EM_API int em_gbdt_metric_sum(const float* margin, const float* Y, int T, int n,
   } else {
     hipLaunchKernelGGL(gbdt_metric_sum, dim3(1), dim3(256), 0, stream, mpart, 0, out);
   }
-  EM_CHECK_LAUNCH();
-  return 0;
+  return launch_status();
 }

@@ -131,8 +131,9 @@ def fit(model, X, bins, nbins, Y, evals, rounds_per_call: int = 500, dp=None):
                node.data_ptr(), node2.data_ptr(), partial.data_ptr(), partial.numel(), Gs.data_ptr(), Hs.data_ptr(), mpart.data_ptr(),
                status.data_ptr(), feat.data_ptr(), sbin.data_ptr(), leaf.data_ptr(), gain.data_ptr(),
                cover.data_ptr(), hist.data_ptr(), qbits,
-               # separate launches instead of the fused round (bit-identity tests; csrc/gbdt.hip), and the
-               # opt-in fused levels (splits inside the next level's histogram pass, EM_GBDT_PRESPLIT)
+               # launch flags (csrc/gbdt.hip, the only switches of the round form): 1 = the separate launches
+               # instead of the fused round (bit-identity tests), 2 = the opt-in presplit levels (splits inside
+               # the next level's histogram pass)
                (1 if getattr(model, "separate_launches", False) else 0)
                | (2 if getattr(model, "presplit_levels", False) else 0), stream)
         hh = hist.view(R, 1 + len(ev_names))[r0:r1].cpu().numpy()

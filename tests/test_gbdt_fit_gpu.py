@@ -255,3 +255,30 @@ def test_62_tasks():
     m = _hip("t62")
     assert m.n_tasks == 62 and m.trees.n_trees == 186
     _check(m, "t62", "9 T = 62")
+
+
+# ----------------------------------------------------------------------------- 10. what the presplit driver carries
+def test_presplit_depth_6():
+    """Levels 1 to 4 are pending splits, their partials alternating between the two halves of the partial
+    buffer (depth 3 has one pending level): the default driver's trees, bit for bit."""
+    m, base = _hip("depth-6", "presplit"), _hip("depth-6")
+    for k in TREE_ARRAYS:
+        assert np.array_equal(getattr(m.trees, k), getattr(base.trees, k)), k
+    _check(m, "depth-6", "10 depth 6 presplit")
+
+
+def test_presplit_chunked_calls(monkeypatch):
+    """rounds_per_call = 3 over 7 rounds on the presplit driver: the arrival total the histogram blocks wait for
+    restarts with each call, beside that call's zeroed counters."""
+    from euromillioner_amd.models import gbdt_hip
+
+    case = "sub-0.8-rounds7"
+    whole = _hip(case)
+    dn, objective, kw = K.CASES[case]
+    X, Y, _ = K.data(dn)
+    monkeypatch.setattr(gbdt_hip, "fit", functools.partial(gbdt_hip.fit, rounds_per_call=3))
+    m = _new(objective, "presplit", **kw).fit(X, Y)
+    assert m.backend_used == "hip"
+    for k in TREE_ARRAYS:
+        assert np.array_equal(getattr(m.trees, k), getattr(whole.trees, k)), k
+    _check(m, case, "10 sub-0.8-rounds7 presplit rounds_per_call 3")
