@@ -59,9 +59,9 @@ def candidates(seed: int, tree: int, node: int, F: int, k: int) -> np.ndarray:
     arr = list(range(F))
     key = np.uint64((tree << 32) | node)
     s = np.uint64((seed ^ CAND_SALT) & 0xFFFFFFFFFFFFFFFF)
+    hs = hash3(s, key, np.arange(min(k, F), dtype=np.uint64))  # (the stream does not depend on the swaps)
     for i in range(min(k, F)):
-        h = int(hash3(s, key, np.uint64(i)))
-        j = i + h % (F - i)
+        j = i + int(hs[i]) % (F - i)
         arr[i], arr[j] = arr[j], arr[i]
     return np.array(arr[:min(k, F)], dtype=np.int64)
 

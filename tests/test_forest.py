@@ -127,6 +127,15 @@ def test_hip_forest_predict_many_trees():
     assert np.allclose(pd, cpu.predict_proba(X[:500]), atol=1e-6)
 
 
+def _check_first_trees(md, n_tr, feat, value, gain, cover, depth, seed, trees=4):
+    """The first trees of a device forest fitted on md[:n_tr] -> md[1:n_tr + 1], node by node from the definition."""
+    from _rf_fit_ref import check_forest
+
+    m = md.cpu().numpy().view(np.uint64)
+    check_forest(m[:n_tr].reshape(-1, 1), m[1:n_tr + 1], 62, feat[:trees].cpu().numpy(), value[:trees].cpu().numpy(),
+                 gain[:trees].cpu().numpy(), cover[:trees].cpu().numpy(), range(trees), depth, 8, 1, True, seed)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("depth", [4, 8])
 def test_hip_forest_predict_matches_torch_traversal(depth):
@@ -140,8 +149,9 @@ def test_hip_forest_predict_matches_torch_traversal(depth):
     nums, _ = generate_draws(20001, seed=0, planted=0.9, native=False)
     md = torch.from_numpy(mask_bits(nums).view(np.int64)).cuda()
     n_tr = 14000
-    feat, value, _, _ = K.fit(md[:n_tr].reshape(-1, 1).contiguous(), md[1:n_tr + 1].contiguous(), 62, 0, 70, depth,
-                              8, 1, True, 0, return_device=True)
+    feat, value, gain, cover = K.fit(md[:n_tr].reshape(-1, 1).contiguous(), md[1:n_tr + 1].contiguous(), 62, 0, 70,
+                                     depth, 8, 1, True, 0, return_device=True)
+    _check_first_trees(md, n_tr, feat, value, gain, cover, depth, 0)
     Xv = md[n_tr:20000].reshape(-1, 1).contiguous()
     p = K.predict(Xv, feat, value, depth)
     x = Xv[:, 0]
@@ -172,8 +182,9 @@ def test_hip_forest_predict_streamed_bit_identical(depth, trees, n):
     nums, _ = generate_draws(20001, seed=1, planted=0.9, native=False)
     md = torch.from_numpy(mask_bits(nums).view(np.int64)).cuda()
     n_tr = 14000
-    feat, value, _, _ = K.fit(md[:n_tr].reshape(-1, 1).contiguous(), md[1:n_tr + 1].contiguous(), 62, 0, trees, depth,
-                              8, 1, True, 0, return_device=True)
+    feat, value, gain, cover = K.fit(md[:n_tr].reshape(-1, 1).contiguous(), md[1:n_tr + 1].contiguous(), 62, 0, trees,
+                                     depth, 8, 1, True, 0, return_device=True)
+    _check_first_trees(md, n_tr, feat, value, gain, cover, depth, 0)
     g = torch.Generator(device="cuda").manual_seed(n)
     Xv = md[torch.randint(0, 20000, (n,), device="cuda", generator=g)].reshape(-1, 1).contiguous()
     for logit in (False, True):
