@@ -12,16 +12,29 @@
 //     (euromillioner_amd/models/forest.py) reproduces every split exactly);
 //   * leaves hold the weighted mean 62-vector (per-output probabilities).
 //
-// Per level (one C++ driver loop on the stream, em_rf_fit):
-//   rf_hist_split  one workgroup per (tree, node): LDS integer histogram hist[f][j] = sum of
-//                  w * x_f * y_j over the node's rows (set bits only: <= 7 x 7 LDS atomics per
-//                  row for one-hot draws), node totals, then a split scan (one wavefront per
-//                  candidate feature, lane j = output j) and the node record;
-//   rf_partition   stable-free ballot partition of the node's row list into its children.
+// All trees advance one level at a time (em_rf_fit, every launch on one stream).  A node's record holds the
+// integer sums S[j] = sum w*y_j, n = sum w and, per candidate feature f, cnt[f] = sum w*x_f and
+// hist[f][j] = sum w*x_f*y_j over its rows (rec_words); rf_split scans the candidates from it (one
+// wavefront per node, lane j = output j).  The row lists come in two forms and each form has its own
+// driver: the row form is the only fork.
+//   Record form (W == 1, F <= 62, N < 2^27: 16-byte records of the row's data), rf_fit_fused:
+//     rf_ycheck + rf_init_rows<true>  root row lists, and the roots' records while the rows are listed;
+//     per level: rf_level_begin       child segments, zeroed counters and the work list, in one workgroup;
+//                rf_split             the split, and the children's totals, zeroed records and candidates;
+//                rf_partition<true>   the children's row lists, and their histograms while the rows move.
+//   Index form (any W: int32 row ids), rf_fit_index:
+//     rf_init_rows<false>             root row lists;
+//     per level: rf_level_prep, rf_worklist   child segments and candidates; the work list;
+//                rf_child_totals      below the root: the node totals from the parent's record;
+//                rf_hist<DERIVE>      the histograms (at the root, DERIVE = false, also the totals);
+//                rf_split, rf_partition<false>.
+// A level's nodes are cut into blocks of rf_chunk(level) rows by the work list (RfWork).
 // Trees are complete binary arrays: node i has children 2i+1 (x_f = 0) and 2i+2 (x_f = 1).
 #include <cstdint>
 #include <cstdlib>
+#include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "draw_topk.h"
@@ -96,41 +109,29 @@ struct RfParams {
   int16_t* cand;  // [T][2^max_depth][k] candidate features of the current level's nodes
   uint32_t* acc;  // [T][2^max_depth][rec] per-node integer sums of the current level (see rec_words)
   int32_t* lrc;   // [T][2^max_depth][2] partition counters (left, right) of the current level
-  const int32_t* yover;  // fused driver: 0 = every row has <= 7 outputs (position-form records), else 1
+  const int32_t* yover;  // record form only: 0 = every row has <= 7 outputs (position-form records), else 1
 };
 
 // per-node record of integer sums: S[64] (sum of w*y_j), n (sum of w), 3 pad, cnt[kp] (sum of w*x_f
 // per candidate), hist[k][64] (sum of w*x_f*y_j) -- exact, so block partials merge with atomics in
 // any order and the split decision is independent of row order and of the block count
-__host__ __device__ inline int rec_words(int k) { return 68 + ((k + 3) & ~3) + 64 * k; }
-// The fused partition's LDS image of a child's cnt / hist words, replicated by lane so the lanes of one
-// atomic mostly hit distinct words: cnt [RF_REP_CNT][kp + 1] (lane & 15), hist [RF_REP_HIST][k * 64 + 16]
+__host__ __device__ constexpr int rec_words(int k) { return 68 + ((k + 3) & ~3) + 64 * k; }
+// The fused partition's LDS image of a child's hist words (a candidate's cnt is word 62 of its row),
+// replicated by lane so the lanes of one atomic mostly hit distinct words: [RF_REP_HIST][k * 64 + 16]
 // (lane & 3; the +16 pad moves a replica's output j to another bank).  Summed at the merge.
-#ifndef RF_REP_CNT
-#define RF_REP_CNT 16
-#endif
 #ifndef RF_REP_HIST
 #define RF_REP_HIST 4
 #endif
-__host__ __device__ inline int rf_rep_cnt_stride(int k) { return ((k + 3) & ~3) + 1; }
-__host__ __device__ inline int rf_rep_hist_stride(int k) { return 64 * k + 16; }
-__host__ __device__ inline int rf_chl_words(int k) {
-  return RF_REP_CNT * rf_rep_cnt_stride(k) + RF_REP_HIST * rf_rep_hist_stride(k);
-}
+__host__ __device__ constexpr int rf_rep_hist_stride(int k) { return 64 * k + 16; }
+__host__ __device__ constexpr int rf_chl_words(int k) { return RF_REP_HIST * rf_rep_hist_stride(k); }
 
 // A row's output bits, extracted once per row: the first 8 positions (-1 = none) + the rest (rows with
 // more than 8 set outputs; a drawn row has 7).  Every candidate bit of the row then adds to its output
 // words with 8 branch-free atomics (an absent position adds 0 to pad word 63: exact integers) instead
 // of a divergent bit-walk loop per candidate -- the loop's ~13 instructions per output were the
 // histogram's cost, not the atomics.
-#ifndef RF_YBITS
-#define RF_YBITS 1
-#endif
-// RF_CNT62: the fused partition counts a candidate's rows (cnt) as output word 62 of its histogram row
-// (no output uses it), so a drawn row's 7 outputs + its count are exactly the 8 unrolled atomics
-#ifndef RF_CNT62
-#define RF_CNT62 1
-#endif
+// A candidate's rows (cnt) are counted as output word 62 of its histogram row (no output uses it: callers
+// pass y | 1 << 62), so a drawn row's 7 outputs + its count are exactly the 8 unrolled atomics.
 struct RfYBits {
   int j[8];
   uint64_t rest;
@@ -186,13 +187,12 @@ EM_DEVICE RfPos rf_pos_unpack(uint64_t yw) {
   p.o[6] = (hi >> 6) & 63u;
   return p;
 }
-// a candidate bit's histogram row: the 7 outputs + the row count as output word 62 (RF_CNT62 layout)
+// a candidate bit's histogram row: the 7 outputs + the row count as output word 62
 EM_DEVICE void rf_add_pos(uint32_t* __restrict__ row, const RfPos& p, uint32_t w) {
 #pragma unroll
   for (int q = 0; q < RF_NPOS; ++q) atomicAdd(&row[p.o[q]], w);
   atomicAdd(&row[62], w);
 }
-static_assert(RF_YBITS && RF_CNT62, "position-form records assume the count-as-word-62 layout");
 
 __global__ void __launch_bounds__(256) rf_ycheck(const uint64_t* __restrict__ Y, int64_t N, int32_t* __restrict__ over) {
   int o = 0;
@@ -203,29 +203,26 @@ __global__ void __launch_bounds__(256) rf_ycheck(const uint64_t* __restrict__ Y,
 // Root row lists: rows with non-zero bootstrap weight, compacted per tree by (blocks x tree)
 // workgroups; each 256-row chunk reserves its output range with one atomic (row order inside a list
 // is irrelevant: every sum is an exact integer).  Root count -> lrc[t][0][0].
-// ROOTH (record rows, the fused driver): the root's histogram record (S, n, candidate cnt / hist) is
+// REC (record rows, the fused driver): the root's histogram record (S, n, candidate cnt / hist) is
 // accumulated while the rows are listed -- the root histogram pass re-read every record (700 MB at
 // 700 k rows x 100 trees) -- in an LDS image per block, added to the zeroed root record at the end.
 EM_DEVICE void rf_node_cands_wave(const RfParams& p, int t, int node, int16_t* __restrict__ co);
 #ifndef RF_INIT_RR
 #define RF_INIT_RR 4
 #endif
-// RF_INIT_REP: the position-form root sums go to lane-replicated LDS images (S by lane & 15, the
-// candidate histograms by lane & 3) summed at the merge: a wave's q-th smallest outputs crowd a few
-// words (the smallest drawn number), and same-word atomics serialise
-#ifndef RF_INIT_REP
-#define RF_INIT_REP 1
-#endif
+// The position-form root sums go to lane-replicated LDS images (S by lane & 15, the candidate histograms
+// by lane & 3) summed at the merge: a wave's q-th smallest outputs crowd a few words (the smallest drawn
+// number), and same-word atomics serialise (the A/B against one image: profiles/r4/rf_ab_round4.txt)
 #ifndef RF_IREP_S
 #define RF_IREP_S 16
 #endif
 #ifndef RF_IREP_H
 #define RF_IREP_H 4
 #endif
-__host__ __device__ inline int rf_init_lds_words(int k) {
-  return ((rec_words(k) + 3) & ~3) + (RF_INIT_REP ? RF_IREP_S * 64 + RF_IREP_H * rf_rep_hist_stride(k) : 0);
+__host__ __device__ constexpr int rf_init_lds_words(int k) {
+  return ((rec_words(k) + 3) & ~3) + (RF_IREP_S * 64 + RF_IREP_H * rf_rep_hist_stride(k));  // the image + its replicas
 }
-template <bool REC, bool ROOTH = false>
+template <bool REC>
 __global__ void __launch_bounds__(RF_NT) rf_init_rows(RfParams p, void* __restrict__ rows_v) {
   // chunks of RR x RF_NT rows: every thread hashes RR rows (all hashes / loads in flight), one count
   // exchange and one atomic reservation per chunk; the count arrays are double-buffered, so a chunk
@@ -235,27 +232,26 @@ __global__ void __launch_bounds__(RF_NT) rf_init_rows(RfParams p, void* __restri
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   __shared__ int wcnt[2][RR][4];
   __shared__ int base[2];
-  extern __shared__ __attribute__((aligned(16))) uint32_t rlds[];  // ROOTH: [rec] image
+  extern __shared__ __attribute__((aligned(16))) uint32_t rlds[];  // REC: [rec] image + the replicas
   __shared__ int8_t rslot[64];
   __shared__ uint64_t rmask;
   __shared__ int16_t rco[RF_MAXF];
   const int k = p.k_feat, rec = rec_words(k), kp = (k + 3) & ~3;
-  const bool pos = ROOTH && p.yover && *p.yover == 0;
+  const bool pos = REC && *p.yover == 0;
   uint32_t my_n = 0;
-  uint32_t* Sr = rlds + ((rec + 3) & ~3);  // RF_INIT_REP images: S [16][64], candidate hist [4][hst]
+  uint32_t* Sr = rlds + ((rec + 3) & ~3);  // the replicas: S [RF_IREP_S][64], candidate hist [RF_IREP_H][hst]
   uint32_t* Hr = Sr + RF_IREP_S * 64;
   const int hst = rf_rep_hist_stride(k);
-  if constexpr (ROOTH) {
+  if constexpr (REC) {
     for (int i = threadIdx.x; i < rf_init_lds_words(k); i += blockDim.x) rlds[i] = 0u;
     if (threadIdx.x < 64) rslot[threadIdx.x] = -1;
     if (wv == 0) rf_node_cands_wave(p, t, 0, rco);
     __syncthreads();
     if (blockIdx.x == 0 && p.max_depth > 0)  // the root's candidates for rf_split (rf_level_begin draws none)
-      for (int i = threadIdx.x; i < (k < p.F ? k : p.F); i += blockDim.x) p.cand[(int64_t)t * k + i] = rco[i];
+      for (int i = threadIdx.x; i < k; i += blockDim.x) p.cand[(int64_t)t * k + i] = rco[i];
     if (threadIdx.x == 0) {
       uint64_t m = 0;
-      const int kk = k < p.F ? k : p.F;
-      for (int i = 0; i < kk; ++i) {
+      for (int i = 0; i < k; ++i) {
         rslot[rco[i]] = (int8_t)i;
         m |= 1ull << rco[i];
       }
@@ -298,14 +294,14 @@ __global__ void __launch_bounds__(RF_NT) rf_init_rows(RfParams p, void* __restri
         if constexpr (REC) {
           const uint64_t xv = p.X[r], yv = p.Y[r];
           const uint32_t wk = (uint32_t)w[k];
-          if (ROOTH && pos) {  // position form: the outputs extracted once, for the record and the root sums
+          if (pos) {  // position form: the outputs extracted once, for the record and the root sums
             const RfPos ps = rf_pos_extract(yv & RF_M62);
             RfRec e = rf_make_rec(xv, 0ull, wk);
             e.y |= rf_pos_pack(ps);
             outr[o + pre[k]] = e;
             my_n += wk;
-            uint32_t* srow = RF_INIT_REP ? Sr + (lane & (RF_IREP_S - 1)) * 64 : rlds;
-            uint32_t* hrow = RF_INIT_REP ? Hr + (lane & (RF_IREP_H - 1)) * hst : rlds + 68 + kp;
+            uint32_t* srow = Sr + (lane & (RF_IREP_S - 1)) * 64;
+            uint32_t* hrow = Hr + (lane & (RF_IREP_H - 1)) * hst;
 #pragma unroll
             for (int q = 0; q < RF_NPOS; ++q) atomicAdd(&srow[ps.o[q]], wk);  // S (none: pad word 63)
             for (uint64_t xx = xv & RF_M62 & rmask; xx; xx &= xx - 1)
@@ -313,7 +309,7 @@ __global__ void __launch_bounds__(RF_NT) rf_init_rows(RfParams p, void* __restri
           } else {
             outr[o + pre[k]] = rf_make_rec(xv, yv, wk);
           }
-          if (ROOTH && !pos) {
+          if (!pos) {  // mask form: the root sums from the mask
             const uint64_t y = yv & RF_M62;
             my_n += wk;
             for (uint64_t yy = y; yy; yy &= yy - 1) atomicAdd(&rlds[__builtin_ctzll(yy)], wk);
@@ -334,14 +330,14 @@ __global__ void __launch_bounds__(RF_NT) rf_init_rows(RfParams p, void* __restri
       off += wcnt[par][k][0] + wcnt[par][k][1] + wcnt[par][k][2] + wcnt[par][k][3];
     }
   }
-  if constexpr (ROOTH) {
+  if constexpr (REC) {
     for (int o = 32; o > 0; o >>= 1) my_n += __shfl_xor(my_n, o);
     if (lane == 0) atomicAdd(&rlds[64], my_n);
     __syncthreads();
     uint32_t* dst = p.acc + (int64_t)t * rec;  // the root record of tree t (zeroed by the driver)
     for (int i = threadIdx.x; i < rec; i += blockDim.x) {
       uint32_t v = 0;
-      if (RF_INIT_REP && pos) {  // sum the replicas
+      if (pos) {  // sum the replicas
         if (i < 62) {
           for (int q = 0; q < RF_IREP_S; ++q) v += Sr[q * 64 + i];
         } else if (i == 64) {
@@ -364,8 +360,7 @@ __global__ void __launch_bounds__(RF_NT) rf_init_rows(RfParams p, void* __restri
 EM_DEVICE void rf_node_cands(const RfParams& p, int t, int node, int16_t* __restrict__ co) {
   int arr[RF_MAXF];
   for (int i = 0; i < p.F; ++i) arr[i] = i;
-  const int kk = p.k_feat < p.F ? p.k_feat : p.F;
-  for (int i = 0; i < kk; ++i) {
+  for (int i = 0; i < p.k_feat; ++i) {  // (k_feat <= F: em_rf_fit)
     const uint64_t h = hash3(p.seed ^ 0x5EEDF00Dull, ((uint64_t)(t + p.t_off) << 32) | (uint64_t)node, (uint64_t)i);
     const int j = i + (int)(h % (uint64_t)(p.F - i));
     const int tmp = arr[i];
@@ -397,8 +392,7 @@ EM_DEVICE void rf_node_cands_wave(const RfParams& p, int t, int node, int16_t* _
       else v[3] = val;
     }
   };
-  const int kk = p.k_feat < p.F ? p.k_feat : p.F;
-  for (int i = 0; i < kk; ++i) {
+  for (int i = 0; i < p.k_feat; ++i) {  // (k_feat <= F: em_rf_fit)
     const uint64_t h = hash3(p.seed ^ 0x5EEDF00Dull, ((uint64_t)(t + p.t_off) << 32) | (uint64_t)node, (uint64_t)i);
     const int j = i + (int)(h % (uint64_t)(p.F - i));
     const int ai = get(i), aj = get(j);
@@ -585,8 +579,8 @@ __global__ void __launch_bounds__(1024) rf_level_begin(RfParams p, int level, in
 // DERIVE (levels >= 1): the node totals S / n are not accumulated here -- rf_child_totals already
 // wrote them from the parent's record (right child = the parent's histogram of its split feature,
 // left = parent - right, exact integers), so a row costs its candidate bits' atomics only.
-template <bool REC, bool DERIVE>
-__global__ void __launch_bounds__(RF_NT) rf_hist(RfParams p, const void* __restrict__ rows_v, int level,
+template <bool DERIVE>
+__global__ void __launch_bounds__(RF_NT) rf_hist(RfParams p, const int32_t* __restrict__ rows, int level,
                                                  const int32_t* __restrict__ wl) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const int nodesL = 1 << level, first = nodesL - 1;
@@ -600,8 +594,7 @@ __global__ void __launch_bounds__(RF_NT) rf_hist(RfParams p, const void* __restr
   const int k = p.k_feat, rec = rec_words(k), kp = (k + 3) & ~3;
   uint32_t* S = lds;                // [64]
   uint32_t* nn = lds + 64;          // [1] (+3 pad)
-  uint32_t* cnt = lds + 68;         // [kp]
-  uint32_t* hist = cnt + kp;        // [k][64]
+  uint32_t* hist = lds + 68 + kp;   // [k][64] (cnt [kp] at 68: counted in hist[c][62], see word())
   __shared__ int16_t slot[RF_MAXF];
   __shared__ uint64_t cmask[RF_MAXF / 64];
   const bool split = level < p.max_depth;
@@ -609,35 +602,23 @@ __global__ void __launch_bounds__(RF_NT) rf_hist(RfParams p, const void* __restr
   for (int i = threadIdx.x; i < p.F; i += blockDim.x) slot[i] = -1;
   if (threadIdx.x < RF_MAXF / 64) cmask[threadIdx.x] = 0ull;
   __syncthreads();
-  const int kk = k < p.F ? k : p.F;
   if (split && threadIdx.x == 0) {
     const int16_t* co = p.cand + ((int64_t)t * nodesL + nd) * k;
-    for (int i = 0; i < kk; ++i) {
+    for (int i = 0; i < k; ++i) {
       slot[co[i]] = (int16_t)i;
       cmask[co[i] >> 6] |= 1ull << (co[i] & 63);
     }
   }
   __syncthreads();
-  const int32_t* rl = static_cast<const int32_t*>(rows_v) + (int64_t)t * p.N + start;
-  const RfRec* rr = static_cast<const RfRec*>(rows_v) + (int64_t)t * p.N + start;
+  const int32_t* rl = rows + (int64_t)t * p.N + start;
   const int i0 = (int)((int64_t)count * wk.j / B), i1 = (int)((int64_t)count * (wk.j + 1) / B);
   uint32_t my_n = 0;
   const bool packed = rf_packed(p.N);
   for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-    int64_t r = 0;
-    uint32_t w;
-    uint64_t y, xr = 0;
-    if constexpr (REC) {
-      const RfRec e = rr[i];
-      w = rf_rec_w(e);
-      y = e.y & RF_M62;
-      xr = e.x & RF_M62;
-    } else {
-      const int32_t e = rl[i];
-      r = packed ? (e & RF_RMASK) : e;
-      w = packed ? (uint32_t)e >> RF_WSHIFT : (uint32_t)row_weight(p.bootstrap, p.seed, t + p.t_off, r);
-      y = p.Y[r] & RF_M62;
-    }
+    const int32_t e = rl[i];
+    const int64_t r = packed ? (e & RF_RMASK) : e;
+    const uint32_t w = packed ? (uint32_t)e >> RF_WSHIFT : (uint32_t)row_weight(p.bootstrap, p.seed, t + p.t_off, r);
+    const uint64_t y = p.Y[r] & RF_M62;
     if (!DERIVE) {  // (every row: the uniform 7-output walk is already branch-coherent)
       my_n += w;
       uint64_t yy = y;
@@ -648,25 +629,13 @@ __global__ void __launch_bounds__(RF_NT) rf_hist(RfParams p, const void* __restr
     }
     if (!split) continue;
     for (int wd = 0; wd < p.W; ++wd) {
-      uint64_t xx = (REC ? xr : p.X[r * p.W + wd]) & cmask[wd];
-      if (RF_YBITS && xx) {  // candidate rows: outputs extracted once, the count as output word 62
+      uint64_t xx = p.X[r * p.W + wd] & cmask[wd];
+      if (xx) {  // candidate rows: outputs extracted once, the count as output word 62
         const RfYBits yb = rf_ybits(y | (1ull << 62));
         while (xx) {
           const int sl = slot[wd * 64 + __builtin_ctzll(xx)];
           xx &= xx - 1;
           rf_add_ybits(hist + sl * 64, yb, w);
-        }
-      }
-      while (!RF_YBITS && xx) {
-        const int sl = slot[wd * 64 + __builtin_ctzll(xx)];
-        xx &= xx - 1;
-        atomicAdd(&cnt[sl], w);
-        {
-          uint64_t y2 = y;
-          while (y2) {
-            atomicAdd(&hist[sl * 64 + __builtin_ctzll(y2)], w);
-            y2 &= y2 - 1;
-          }
         }
       }
     }
@@ -679,8 +648,8 @@ __global__ void __launch_bounds__(RF_NT) rf_hist(RfParams p, const void* __restr
   uint32_t* dst = p.acc + ((int64_t)t * nodesL + nd) * rec;
   const int used = split ? rec : 68;
   const int lo = DERIVE ? 68 : 0;  // S / n (words 0..67) already hold the derived totals
-  auto word = [&](int i) -> uint32_t {  // RF_YBITS: cnt[c] was counted in hist[c][62]
-    if (!RF_YBITS || i < 68) return lds[i];
+  auto word = [&](int i) -> uint32_t {  // cnt[c] was counted in hist[c][62]
+    if (i < 68) return lds[i];
     if (i < 68 + kp) return i - 68 < k ? lds[68 + kp + (i - 68) * 64 + 62] : 0u;
     return ((i - 68 - kp) & 63) < 62 ? lds[i] : 0u;
   };
@@ -749,16 +718,15 @@ __global__ void __launch_bounds__(128) rf_split(RfParams p, int level, uint32_t*
   if (can_split) {
     uint64_t s2 = (uint64_t)Sj * Sj;
     for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
-    const int kk = k < p.F ? k : p.F;
     const int16_t* co = p.cand + ((int64_t)t * nodesL + nd) * k;
     // candidates in batches of 8 whose record words are all loaded first: one global round trip per
     // batch instead of one per candidate (the serial loads were ~12 us of every level's split)
-    for (int c0 = 0; c0 < kk; c0 += 8) {
+    for (int c0 = 0; c0 < k; c0 += 8) {
       int fb[8];
       uint32_t nRb[8], SRb[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int c = c0 + u < kk ? c0 + u : kk - 1;
+        const int c = c0 + u < k ? c0 + u : k - 1;
         fb[u] = co[c];
         nRb[u] = A[68 + c];
         SRb[u] = lane < 62 ? A[68 + kp + c * 64 + lane] : 0u;
@@ -766,7 +734,7 @@ __global__ void __launch_bounds__(128) rf_split(RfParams p, int level, uint32_t*
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int c = c0 + u;
-        if (c >= kk) break;
+        if (c >= k) break;
         const int f = fb[u];
         const uint32_t nR = nRb[u], nL = n - nR;
         const uint32_t SR = SRb[u];
@@ -826,13 +794,13 @@ __global__ void __launch_bounds__(128) rf_split(RfParams p, int level, uint32_t*
 // K10: children row lists, (blocks x nodes x trees) workgroups: left rows (x_f = 0) fill the parent
 // segment from its start, right rows from its end; every 256-row chunk reserves its ranges with one
 // atomic per side on the node's counters (lrc), which rf_level_prep turns into the child segments.
-// HIST (record rows, derived node totals): while a record moves to its child, its candidate bits are
+// REC (record rows, derived node totals): while a record moves to its child, its candidate bits are
 // also added to that child's histogram (cnt / hist words of the child's record in acc_next, LDS partials
 // merged by integer atomics), so level + 1 needs no histogram pass over its rows.
 #ifndef RF_PART_RR
 #define RF_PART_RR 4
 #endif
-template <bool REC, bool HIST>
+template <bool REC>
 __global__ void __launch_bounds__(RF_NT) rf_partition(RfParams p, const void* __restrict__ rin_v,
                                                       void* __restrict__ rout_v, int level,
                                                       const int32_t* __restrict__ wl, uint32_t* __restrict__ acc_next,
@@ -849,21 +817,20 @@ __global__ void __launch_bounds__(RF_NT) rf_partition(RfParams p, const void* __
   const int start = sg[0], count = sg[1];
   const int f = p.feat[(int64_t)t * p.nodes + node];
   if (f < 0 || count < 0) return;
-  extern __shared__ __attribute__((aligned(16))) uint32_t chl[];  // HIST: [2 children][rec]
+  extern __shared__ __attribute__((aligned(16))) uint32_t chl[];  // REC: [2 children][rf_chl_words]
   __shared__ int8_t cslot[2][64];
   __shared__ uint64_t cmk[2];
   const int kf = p.k_feat, rec = rec_words(kf), kp = (kf + 3) & ~3;
-  const int chw = rf_chl_words(kf), cst = rf_rep_cnt_stride(kf), hst = rf_rep_hist_stride(kf);
-  const int lane_c = (threadIdx.x & 63) % RF_REP_CNT, lane_h = (threadIdx.x & 63) % RF_REP_HIST;
-  const bool pos = HIST && REC && p.yover && *p.yover == 0;
-  if (HIST) {
+  const int chw = rf_chl_words(kf), hst = rf_rep_hist_stride(kf);
+  const int lane_h = (threadIdx.x & 63) % RF_REP_HIST;
+  const bool pos = REC && *p.yover == 0;
+  if (REC) {
     for (int i = threadIdx.x; i < 2 * chw; i += blockDim.x) chl[i] = 0u;
     if (threadIdx.x < 2) {
       const int s = threadIdx.x;
       const int16_t* co = cand_next + ((int64_t)t * (2 * nodesL) + 2 * nd + s) * kf;
       uint64_t m = 0;
-      const int kk = kf < p.F ? kf : p.F;
-      for (int i = 0; i < kk; ++i) {
+      for (int i = 0; i < kf; ++i) {
         cslot[s][co[i]] = (int8_t)i;
         m |= 1ull << co[i];
       }
@@ -932,7 +899,7 @@ __global__ void __launch_bounds__(RF_NT) rf_partition(RfParams p, const void* __
         roff += rc[buf][k][q];
       }
     }
-    if constexpr (HIST && REC) {
+    if constexpr (REC) {
 #pragma unroll
       for (int k2 = 0; k2 < RR; ++k2) {
         if (!have[k2]) continue;
@@ -940,8 +907,7 @@ __global__ void __launch_bounds__(RF_NT) rf_partition(RfParams p, const void* __
         const uint32_t w = rf_rec_w(r[k2]);
         const uint64_t y = r[k2].y & RF_M62;
         uint64_t xx = r[k2].x & RF_M62 & cmk[sd];
-        uint32_t* cnt = chl + sd * chw + lane_c * cst;
-        uint32_t* hist = chl + sd * chw + RF_REP_CNT * cst + lane_h * hst;
+        uint32_t* hist = chl + sd * chw + lane_h * hst;
         if (pos) {  // position-form record: the outputs are 7 bit fields
           if (xx) {
             const RfPos ps = rf_pos_unpack(r[k2].y);
@@ -949,29 +915,18 @@ __global__ void __launch_bounds__(RF_NT) rf_partition(RfParams p, const void* __
           }
           continue;
         }
-        if (RF_YBITS && xx) {
-          const RfYBits yb = rf_ybits(RF_CNT62 ? (y | (1ull << 62)) : y);
+        if (xx) {  // mask-form record: outputs extracted once, the count as output word 62
+          const RfYBits yb = rf_ybits(y | (1ull << 62));
           while (xx) {
             const int sl = cslot[sd][__builtin_ctzll(xx)];
             xx &= xx - 1;
-            if (!RF_CNT62) atomicAdd(&cnt[sl], w);
             rf_add_ybits(hist + sl * 64, yb, w);
-          }
-        }
-        while (!RF_YBITS && xx) {
-          const int sl = cslot[sd][__builtin_ctzll(xx)];
-          xx &= xx - 1;
-          atomicAdd(&cnt[sl], w);
-          uint64_t y2 = y;
-          while (y2) {
-            atomicAdd(&hist[sl * 64 + __builtin_ctzll(y2)], w);
-            y2 &= y2 - 1;
           }
         }
       }
     }
   }
-  if constexpr (HIST) {
+  if constexpr (REC) {
     __syncthreads();
 #pragma unroll
     for (int sd = 0; sd < 2; ++sd) {
@@ -979,16 +934,12 @@ __global__ void __launch_bounds__(RF_NT) rf_partition(RfParams p, const void* __
       const uint32_t* src = chl + sd * chw;
       for (int i = 68 + threadIdx.x; i < rec; i += blockDim.x) {
         uint32_t v = 0;
-        if (i < 68 + kp) {  // cnt[sl]: its replicas (RF_CNT62: word 62 of the slot's histogram row)
-          if (RF_YBITS && RF_CNT62) {
-            if (i - 68 < kf)
-              for (int q = 0; q < RF_REP_HIST; ++q) v += src[RF_REP_CNT * cst + q * hst + (i - 68) * 64 + 62];
-          } else {
-            for (int q = 0; q < RF_REP_CNT; ++q) v += src[q * cst + (i - 68)];
-          }
-        } else if (!(RF_YBITS && RF_CNT62) || ((i - 68 - kp) & 63) < 62) {  // hist[sl][j]: its replicas
+        if (i < 68 + kp) {  // cnt[sl]: word 62 of the slot's histogram row, its replicas
+          if (i - 68 < kf)
+            for (int q = 0; q < RF_REP_HIST; ++q) v += src[q * hst + (i - 68) * 64 + 62];
+        } else if (((i - 68 - kp) & 63) < 62) {  // hist[sl][j]: its replicas
           const int o = i - 68 - kp;
-          for (int q = 0; q < RF_REP_HIST; ++q) v += src[RF_REP_CNT * cst + q * hst + o];
+          for (int q = 0; q < RF_REP_HIST; ++q) v += src[q * hst + o];
         }
         if (B == 1)  // the node's only block: plain stores (rf_split did not zero these words)
           dst[i] = v;
@@ -1369,14 +1320,6 @@ EM_API int em_rf_nodes(int max_depth) { return (1 << (max_depth + 1)) - 1; }
 // bits 62/63 free for the weight) or 4 (index form)
 EM_API int em_rf_row_bytes(int W, int F, int64_t N) { return (W == 1 && F <= 62 && N <= (int64_t)RF_RMASK) ? 16 : 4; }
 
-// per-level launch shape: blocks per node from the average node size (>= 4096 rows per block)
-static void rf_shape(int64_t N, int level, int& B, int& nt) {
-  const int64_t avg = N / (1ll << level);
-  int64_t b = avg / 4096;
-  B = (int)(b < 1 ? 1 : (b > 64 ? 64 : b));
-  nt = avg >= 2048 ? RF_NT : 64;
-}
-
 EM_API int64_t em_rf_acc_words(int T, int max_depth, int k_feat) {
   if (T < 1 || max_depth < 0 || max_depth > 14 || k_feat < 1 || k_feat > RF_MAXF) return -1;
   // two levels' records (rf_child_totals) + a second candidate buffer (the fused partition fills the
@@ -1385,8 +1328,135 @@ EM_API int64_t em_rf_acc_words(int T, int max_depth, int k_feat) {
   return 2 * (int64_t)T * (1ll << max_depth) * rec_words(k_feat) + ((int64_t)T * (1ll << max_depth) * k_feat + 1) / 2 + 1;
 }
 
-// Native level-wise driver: all T trees advance one level per (prep, hist, split, partition) round.
-// scratch: cand int16 [T][2^D][k], acc uint32 [em_rf_acc_words], lrc int32 [T][2^D][2]
+namespace {
+
+// Every dynamic LDS image fits at the widest candidate count its kernels see: a node record for rf_hist
+// (k <= F <= RF_MAXF), the fused kernels' replicated images in record form (k <= F <= 62).
+constexpr int RF_LDS_MAX = 160 * 1024 - 8192;
+static_assert(rec_words(RF_MAXF) * 4 <= RF_LDS_MAX, "rf_hist: the node record");
+static_assert(2 * rf_chl_words(62) * 4 <= RF_LDS_MAX, "rf_partition<true>: the two child images");
+static_assert(rf_init_lds_words(62) * 4 <= RF_LDS_MAX, "rf_init_rows<true>: the root image and its replicas");
+
+// what em_rf_fit decides once, for both drivers
+struct RfPlan {
+  bool rec_rows;       // record-form row lists (rf_fit_fused), else index form (rf_fit_index)
+  int nodes, rec;      // nodes per tree, words per node record
+  uint32_t* accs[2];   // node records of the even / odd levels, carved from acc
+  int16_t* cands[2];   // candidate lists of the even / odd levels: cand, and the tail of acc
+  int32_t* yover;      // rf_ycheck's flag, the last word of acc (record form)
+  int64_t kept;        // expected rows per tree
+};
+
+void rf_set_lds_attrs() {
+  static const bool once = [] {
+    for (const void* f : {(const void*)rf_hist<false>, (const void*)rf_hist<true>, (const void*)rf_partition<true>,
+                          (const void*)rf_init_rows<true>})
+      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, RF_LDS_MAX);
+    return true;
+  }();
+  (void)once;
+}
+
+// listing blocks per tree: one per 4096 rows, 1 .. 64
+int rf_list_blocks(int64_t N) {
+  const int64_t b = N / 4096;
+  return (int)(b < 1 ? 1 : (b > 64 ? 64 : b));
+}
+// threads per block of a level's work-list kernels, from the average node's rows
+int rf_level_threads(int64_t kept, int level) { return (kept >> level) >= 2048 ? RF_NT : 64; }
+// their grid: an upper bound of the work list (kept rows per tree <= N; the kernels exit past its end)
+unsigned rf_level_grid(int64_t N, int T, int level) {
+  const int64_t gmax = (int64_t)T * ((N + RF_CHUNK - 1) / RF_CHUNK + 1) + ((int64_t)T << level);
+  return (unsigned)(gmax < 0x7FFFFFFF ? gmax : 0x7FFFFFFF);
+}
+// this level's node records and candidate lists (double-buffered: the next level's are filled meanwhile)
+void rf_level_buffers(const RfPlan& pl, RfParams& p, int level) {
+  p.acc = pl.accs[level & 1];
+  p.cand = pl.cands[level & 1];
+}
+
+// Root row lists into rows_a, root counts into lrc; record form: also the roots' records into accs[0]
+// and the record form (position / mask) into yover, decided on the device.
+int rf_list_rows(const RfPlan& pl, const RfParams& p, void* rows_a, hipStream_t stream) {
+  const dim3 grid(rf_list_blocks(p.N), p.T);
+  (void)hipMemsetAsync(p.lrc, 0, (size_t)p.T * 2 * sizeof(int32_t), stream);
+  if (pl.rec_rows) {
+    (void)hipMemsetAsync(pl.accs[0], 0, (size_t)p.T * pl.rec * sizeof(uint32_t), stream);
+    (void)hipMemsetAsync(pl.yover, 0, sizeof(int32_t), stream);
+    const int64_t yb = (p.N + 255) / 256;
+    hipLaunchKernelGGL(rf_ycheck, dim3((unsigned)(yb < 1024 ? yb : 1024)), dim3(256), 0, stream, p.Y, p.N, pl.yover);
+    hipLaunchKernelGGL(rf_init_rows<true>, grid, dim3(RF_NT), (size_t)rf_init_lds_words(p.k_feat) * 4, stream, p,
+                       rows_a);
+  } else {
+    hipLaunchKernelGGL(rf_init_rows<false>, grid, dim3(RF_NT), 0, stream, p, rows_a);
+  }
+  EM_CHECK_LAUNCH();
+  return 0;
+}
+
+// Record form.  Per level: rf_level_begin (segments, counters, work list), rf_split (also the children's
+// totals, zeroed records and candidates), the partition (also the children's histograms) -- 3 launches;
+// the roots' records came with the row lists.
+// Variants measured slower and removed in round 5 (docs/DESIGN.md §2 keeps their numbers): the
+// matrix-core histogram (rf_hist_mfma: 7.0 vs 6.2 ms), node totals accumulated at every level instead
+// of derived from the parent (8.45 vs 6.67 ms), a separate histogram pass at every level (6.0 vs
+// 4.8-5.2 ms).
+int rf_fit_fused(const RfPlan& pl, RfParams p, void* rin, void* rout, int32_t* wl, hipStream_t stream) {
+  for (int level = 0; level <= p.max_depth; ++level) {
+    rf_level_buffers(pl, p, level);
+    hipLaunchKernelGGL(rf_level_begin, dim3(1), dim3(1024), 0, stream, p, level, wl, 0);
+    uint32_t* an = level < p.max_depth ? pl.accs[(level + 1) & 1] : nullptr;
+    int16_t* cn = level + 1 < p.max_depth ? pl.cands[(level + 1) & 1] : nullptr;
+    hipLaunchKernelGGL(rf_split, dim3(1 << level, p.T), dim3(cn ? 128 : 64), 0, stream, p, level, an, cn);
+    EM_CHECK_LAUNCH();
+    // rf_split of the level before the last wrote the last level's leaves (their rows are never read)
+    if (level + 1 >= p.max_depth) break;
+    hipLaunchKernelGGL(rf_partition<true>, dim3(rf_level_grid(p.N, p.T, level)), dim3(rf_level_threads(pl.kept, level)),
+                       (size_t)2 * rf_chl_words(p.k_feat) * 4, stream, p, (const void*)rin, rout, level,
+                       (const int32_t*)wl, an, (const int16_t*)cn);
+    EM_CHECK_LAUNCH();
+    std::swap(rin, rout);
+  }
+  return 0;
+}
+
+// Index form.  Per level: rf_level_prep + rf_worklist, the records zeroed, below the root rf_child_totals
+// (node totals derived from the parent's histogram), rf_hist, rf_split, the counters zeroed, the partition.
+int rf_fit_index(const RfPlan& pl, RfParams p, void* rin, void* rout, int32_t* wl, hipStream_t stream) {
+  for (int level = 0; level <= p.max_depth; ++level) {
+    const int nodesL = 1 << level;
+    const int64_t tn = (int64_t)p.T * nodesL;
+    const dim3 grid(rf_level_grid(p.N, p.T, level)), block(rf_level_threads(pl.kept, level));
+    const size_t lds = (size_t)pl.rec * 4;
+    rf_level_buffers(pl, p, level);
+    hipLaunchKernelGGL(rf_level_prep, dim3((unsigned)((tn + 127) / 128)), dim3(128), 0, stream, p, level);
+    hipLaunchKernelGGL(rf_worklist, dim3(1), dim3(1024), 0, stream, p, level, wl);
+    (void)hipMemsetAsync(p.acc, 0, (size_t)tn * pl.rec * sizeof(uint32_t), stream);
+    if (level == 0) {
+      hipLaunchKernelGGL(rf_hist<false>, grid, block, lds, stream, p, (const int32_t*)rin, level, (const int32_t*)wl);
+    } else {
+      hipLaunchKernelGGL(rf_child_totals, dim3(nodesL, p.T), dim3(64), 0, stream, p, pl.accs[(level - 1) & 1], level);
+      if (level < p.max_depth)  // (the last level needs node totals only: all derived)
+        hipLaunchKernelGGL(rf_hist<true>, grid, block, lds, stream, p, (const int32_t*)rin, level, (const int32_t*)wl);
+    }
+    hipLaunchKernelGGL(rf_split, dim3(nodesL, p.T), dim3(64), 0, stream, p, level, (uint32_t*)nullptr,
+                       (int16_t*)nullptr);
+    EM_CHECK_LAUNCH();
+    if (level == p.max_depth) break;
+    (void)hipMemsetAsync(p.lrc, 0, (size_t)tn * 2 * sizeof(int32_t), stream);
+    hipLaunchKernelGGL(rf_partition<false>, grid, block, 0, stream, p, (const void*)rin, rout, level,
+                       (const int32_t*)wl, (uint32_t*)nullptr, (const int16_t*)nullptr);
+    EM_CHECK_LAUNCH();
+    std::swap(rin, rout);
+  }
+  return 0;
+}
+
+}  // namespace
+
+// Native level-wise fit of T trees: the row lists, then one driver loop over the levels, by row form.
+// scratch: rows_a / rows_b [T][N] rows of em_rf_row_bytes, cand int16 [T][2^D][k], acc uint32
+// [em_rf_acc_words], lrc int32 [T][2^D][2], wl int32 work list
 EM_API int em_rf_fit(const uint64_t* X, int W, const uint64_t* Y, int64_t N, int F, int T, int max_depth, int k_feat,
                      int min_leaf, int bootstrap, uint64_t seed, int t_off, void* rows_a, void* rows_b,
                      int32_t* seg, int16_t* feat, float* value, double* gain, float* cover, int16_t* cand,
@@ -1394,141 +1464,24 @@ EM_API int em_rf_fit(const uint64_t* X, int W, const uint64_t* Y, int64_t N, int
   if (!X || !Y || !rows_a || !rows_b || !seg || !feat || !value || !gain || !cover || !cand || !acc || !lrc || !wl)
     return EM_ERR_ARG;
   if (W < 1 || F < 1 || F > RF_MAXF || F > 64 * W || T < 1 || max_depth < 0 || max_depth > 14 || k_feat < 1 ||
-      k_feat > RF_MAXF || min_leaf < 1 || N < 1 || N >= (1ll << 31))
+      k_feat > F || min_leaf < 1 || N < 1 || N >= (1ll << 31))
     return EM_ERR_ARG;
-  const int nodes = (1 << (max_depth + 1)) - 1;
-  const int rec = rec_words(k_feat);
-  const size_t lds = (size_t)rec * 4;
-  if (lds > 160 * 1024 - 8192) return EM_ERR_ARG;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)rf_hist<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 8192);
-    (void)hipFuncSetAttribute((const void*)rf_hist<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 8192);
-    (void)hipFuncSetAttribute((const void*)rf_hist<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 8192);
-    (void)hipFuncSetAttribute((const void*)rf_hist<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 8192);
-    (void)hipFuncSetAttribute((const void*)rf_partition<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 8192);
-    attr = true;
-  }
-  // record-form row lists for one-word features (rows_a/rows_b hold 16 B per row: em_rf_row_bytes).
-  // Variants measured slower and removed in round 5 (docs/DESIGN.md §2 keeps their numbers): the
-  // matrix-core histogram (rf_hist_mfma: 7.0 vs 6.2 ms), node totals accumulated at every level instead
-  // of derived from the parent (8.45 vs 6.67 ms), a separate histogram pass at every level (6.0 vs
-  // 4.8-5.2 ms).
-  const bool rec_rows = em_rf_row_bytes(W, F, N) == 16;
-  uint32_t* accs[2] = {acc, acc + (int64_t)T * (1ll << max_depth) * rec};
-  int16_t* cands[2] = {cand, reinterpret_cast<int16_t*>(acc + 2 * (int64_t)T * (1ll << max_depth) * rec)};
-  // (the fused partition's replicated child images must fit the LDS: k <= ~70 candidates)
-  const bool fuse = rec_rows && (size_t)2 * rf_chl_words(k_feat) * 4 <= 160 * 1024 - 8192 &&
-                    (size_t)rf_init_lds_words(k_feat) * 4 <= 160 * 1024 - 8192;
-  int32_t* yover = reinterpret_cast<int32_t*>(acc) + em_rf_acc_words(T, max_depth, k_feat) - 1;
-  RfParams p{X, Y, N, W, F, T, max_depth, k_feat, min_leaf, bootstrap, t_off, nodes, seed, seg, feat, value, gain,
-             cover, cand, accs[0], lrc, fuse ? yover : nullptr};
-  (void)hipMemsetAsync(lrc, 0, (size_t)T * 2 * sizeof(int32_t), stream);
-  {
-    int B, nt;
-    rf_shape(N, 0, B, nt);
-    if (fuse) {  // the root records are accumulated by the listing pass
-      (void)hipMemsetAsync(accs[0], 0, (size_t)T * rec * sizeof(uint32_t), stream);
-      (void)hipMemsetAsync(yover, 0, sizeof(int32_t), stream);  // record form decided on the device
-      const int64_t yb = (N + 255) / 256;
-      hipLaunchKernelGGL(rf_ycheck, dim3((unsigned)(yb < 1024 ? yb : 1024)), dim3(256), 0, stream, Y, N, yover);
-      static bool ra = false;
-      if (!ra) {
-        (void)hipFuncSetAttribute((const void*)rf_init_rows<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024 - 8192);
-        ra = true;
-      }
-      hipLaunchKernelGGL((rf_init_rows<true, true>), dim3(B, T), dim3(RF_NT), (size_t)rf_init_lds_words(k_feat) * 4,
-                         stream, p, (void*)rows_a);
-    } else if (rec_rows)
-      hipLaunchKernelGGL(rf_init_rows<true>, dim3(B, T), dim3(RF_NT), 0, stream, p, (void*)rows_a);
-    else
-      hipLaunchKernelGGL(rf_init_rows<false>, dim3(B, T), dim3(RF_NT), 0, stream, p, (void*)rows_a);
-  }
-  EM_CHECK_LAUNCH();
-  void* rin = rows_a;
-  void* rout = rows_b;
-  const int64_t kept = bootstrap ? (N * 632) / 1000 : N;  // expected rows per tree (Poisson(1): 1 - 1/e)
-  if (fuse) {
-    // per level: rf_level_begin (segments, counters, work list), rf_split (also the children's totals,
-    // zeroed records and candidates), the partition (also the children's histograms while a next
-    // level still splits) -- 3 launches per level; the root's record came with the row lists
-    for (int level = 0; level <= max_depth; ++level) {
-      const int nodesL = 1 << level;
-      int B, nt;
-      rf_shape(kept, level, B, nt);
-      (void)B;
-      const int64_t tn = (int64_t)T * nodesL;
-      p.acc = accs[level & 1];
-      p.cand = cands[level & 1];
-      hipLaunchKernelGGL(rf_level_begin, dim3(1), dim3(1024), 0, stream, p, level, wl, 0);
-      const int64_t gmax = (int64_t)T * ((N + RF_CHUNK - 1) / RF_CHUNK + 1) + tn;
-      const unsigned G = (unsigned)(gmax < 0x7FFFFFFF ? gmax : 0x7FFFFFFF);
-      uint32_t* an = level < max_depth ? accs[(level + 1) & 1] : nullptr;
-      int16_t* cn = level + 1 < max_depth ? cands[(level + 1) & 1] : nullptr;
-      hipLaunchKernelGGL(rf_split, dim3(nodesL, T), dim3(cn ? 128 : 64), 0, stream, p, level, an, cn);
-      EM_CHECK_LAUNCH();
-      // rf_split of the level before the last wrote the last level's leaves (their rows are never read)
-      if (level + 1 >= max_depth) break;
-      hipLaunchKernelGGL((rf_partition<true, true>), dim3(G), dim3(nt), (size_t)2 * rf_chl_words(k_feat) * 4, stream,
-                         p, (const void*)rin, rout,
-                         level, (const int32_t*)wl, an, (const int16_t*)cn);
-      EM_CHECK_LAUNCH();
-      void* tmp = rin;
-      rin = rout;
-      rout = tmp;
-    }
-    return 0;
-  }
-  for (int level = 0; level <= max_depth; ++level) {
-    const int nodesL = 1 << level;
-    int B, nt;
-    rf_shape(kept, level, B, nt);
-    const int64_t tn = (int64_t)T * nodesL;
-    p.acc = accs[level & 1];  // this level's node records and candidate lists (double-buffered)
-    p.cand = cands[level & 1];
-    hipLaunchKernelGGL(rf_level_prep, dim3((unsigned)((tn + 127) / 128)), dim3(128), 0, stream, p, level);
-    hipLaunchKernelGGL(rf_worklist, dim3(1), dim3(1024), 0, stream, p, level, wl);
-    // grid: an upper bound of the work list (the kernels exit past wl[tn])
-    const int64_t gmax = (int64_t)T * ((N + RF_CHUNK - 1) / RF_CHUNK + 1) + tn;  // kept rows per tree <= N
-    const unsigned G = (unsigned)(gmax < 0x7FFFFFFF ? gmax : 0x7FFFFFFF);
-    (void)B;
-    (void)hipMemsetAsync(p.acc, 0, (size_t)tn * rec * sizeof(uint32_t), stream);
-    const bool dl = level > 0;  // node totals derived from the parent's histogram below the root
-    if (dl) hipLaunchKernelGGL(rf_child_totals, dim3(nodesL, T), dim3(64), 0, stream, p, accs[(level - 1) & 1], level);
-    if (dl && level == max_depth)
-      ;  // the last level needs node totals only: all derived
-    else if (rec_rows && dl)
-      hipLaunchKernelGGL((rf_hist<true, true>), dim3(G), dim3(nt), lds, stream, p, (const void*)rin, level, (const int32_t*)wl);
-    else if (rec_rows)
-      hipLaunchKernelGGL((rf_hist<true, false>), dim3(G), dim3(nt), lds, stream, p, (const void*)rin, level, (const int32_t*)wl);
-    else if (dl)
-      hipLaunchKernelGGL((rf_hist<false, true>), dim3(G), dim3(nt), lds, stream, p, (const void*)rin, level, (const int32_t*)wl);
-    else
-      hipLaunchKernelGGL((rf_hist<false, false>), dim3(G), dim3(nt), lds, stream, p, (const void*)rin, level, (const int32_t*)wl);
-    hipLaunchKernelGGL(rf_split, dim3(nodesL, T), dim3(64), 0, stream, p, level, (uint32_t*)nullptr,
-                       (int16_t*)nullptr);
-    EM_CHECK_LAUNCH();
-    if (level == max_depth) break;
-    (void)hipMemsetAsync(lrc, 0, (size_t)tn * 2 * sizeof(int32_t), stream);
-    if (rec_rows) {
-      hipLaunchKernelGGL((rf_partition<true, false>), dim3(G), dim3(nt), 0, stream, p, (const void*)rin, rout, level,
-                         (const int32_t*)wl, (uint32_t*)nullptr, (const int16_t*)nullptr);
-    } else {
-      hipLaunchKernelGGL((rf_partition<false, false>), dim3(G), dim3(nt), 0, stream, p, (const void*)rin, rout, level,
-                         (const int32_t*)wl, (uint32_t*)nullptr, (const int16_t*)nullptr);
-    }
-    EM_CHECK_LAUNCH();
-    void* tmp = rin;
-    rin = rout;
-    rout = tmp;
-  }
-  return 0;
+  RfPlan pl;
+  pl.rec_rows = em_rf_row_bytes(W, F, N) == 16;  // (then F <= 62: the fused kernels' LDS images fit, see above)
+  pl.nodes = (1 << (max_depth + 1)) - 1;
+  pl.rec = rec_words(k_feat);
+  const int64_t level_words = (int64_t)T * (1ll << max_depth) * pl.rec;
+  pl.accs[0] = acc;
+  pl.accs[1] = acc + level_words;
+  pl.cands[0] = cand;
+  pl.cands[1] = reinterpret_cast<int16_t*>(acc + 2 * level_words);
+  pl.yover = pl.rec_rows ? reinterpret_cast<int32_t*>(acc) + em_rf_acc_words(T, max_depth, k_feat) - 1 : nullptr;
+  pl.kept = bootstrap ? (N * 632) / 1000 : N;  // Poisson(1) weights: 1 - 1/e of the rows
+  const RfParams p{X, Y, N, W, F, T, max_depth, k_feat, min_leaf, bootstrap, t_off, pl.nodes, seed, seg, feat, value,
+                   gain, cover, cand, pl.accs[0], lrc, pl.yover};
+  rf_set_lds_attrs();
+  if (const int e = rf_list_rows(pl, p, rows_a, stream)) return e;
+  return pl.rec_rows ? rf_fit_fused(pl, p, rows_a, rows_b, wl, stream) : rf_fit_index(pl, p, rows_a, rows_b, wl, stream);
 }
 
 // scratch bytes em_rf_predict's tree-streamed path needs (0: that path does not apply)

@@ -19,8 +19,8 @@ RF_CHUNK0 = 32768      # RF_CHUNK0: rows per block of a root node (rf_chunk(0))
 RF_CHUNK1 = 8192       # RF_CHUNK1: rows per block at level 1
 RF_CHUNK = 8192        # RF_CHUNK: rows per block from level 2 on
 RF_BEGIN_LDS = 16384   # RF_BEGIN_LDS: work-list items whose block counts rf_level_begin keeps in LDS
-RF_SHAPE_NT_ROWS = 2048     # rf_shape: nt = avg >= 2048 ? 256 : 64
-RF_SHAPE_BLOCK_ROWS = 4096  # rf_shape: root listing blocks per tree = N / 4096 (1 .. 64)
+RF_SHAPE_NT_ROWS = 2048     # rf_level_threads: (kept >> level) >= 2048 ? 256 : 64
+RF_SHAPE_BLOCK_ROWS = 4096  # rf_list_blocks: root listing blocks per tree = N / 4096 (1 .. 64)
 RF_BEGIN_BATCH = 8 * 1024   # rf_level_begin: items per batch (PB = 8 per thread x 1024 threads)
 
 
@@ -95,10 +95,23 @@ def test_thresholds_mirror_the_driver():
     assert one(r"#define RF_CHUNK1 (\d+)") == RF_CHUNK1
     assert one(r"constexpr int RF_CHUNK = (\d+);") == RF_CHUNK
     assert one(r"constexpr int RF_BEGIN_LDS = (\d+);") == RF_BEGIN_LDS
-    assert one(r"nt = avg >= (\d+) \? RF_NT : 64;") == RF_SHAPE_NT_ROWS
-    assert one(r"int64_t b = avg / (\d+);") == RF_SHAPE_BLOCK_ROWS
+    assert one(r"return \(kept >> level\) >= (\d+) \? RF_NT : 64;") == RF_SHAPE_NT_ROWS
+    assert one(r"const int64_t b = N / (\d+);") == RF_SHAPE_BLOCK_ROWS
     assert one(r"constexpr int PB = (\d+);") * one(r"g0 \+= PB \* (\d+)\)") == RF_BEGIN_BATCH
     assert "level == 0 ? RF_CHUNK0 : (level == 1 ? RF_CHUNK1 : RF_CHUNK)" in src  # chunk() below
+
+
+@gpu
+def test_more_candidates_than_features_is_rejected():
+    """k > F would leave candidate slots that are never filled: em_rf_fit refuses it before any launch."""
+    from euromillioner_amd.ops import forest as K
+
+    X = np.arange(1, 9, dtype=np.uint64).reshape(8, 1)
+    Y = np.arange(8, 0, -1, dtype=np.uint64)
+    with pytest.raises(ValueError, match="em_rf_fit"):
+        K.fit(X, Y, 62, 0, 1, 1, 63, 1, False, 0)
+    feat, _, _, cover = K.fit(X, Y, 62, 0, 1, 1, 62, 1, False, 0)  # k == F is the limit, and fits
+    assert feat.shape == (1, 3) and cover[0, 0] == 8
 
 
 # ------------------------------------------------------------------ multi-block nodes, fused record path
