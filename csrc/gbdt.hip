@@ -230,7 +230,7 @@ struct SplitFinal {
   int max_depth = 0;
 };
 EM_DEVICE void prune_task(int8_t* st, int16_t* fe, const float* gn, int max_depth, float gamma);
-template <typename A, bool COH, int NPRE = 32>
+template <typename A, bool COH, int NPRE>
 EM_DEVICE void split_body(int vb, char* smem, const A* __restrict__ hist, int nchunks, int64_t cstride,
                           const int* __restrict__ foff, int T, int F, int C, int level, int NN, double* __restrict__ G,
                           double* __restrict__ H, int8_t* __restrict__ status, int16_t* __restrict__ feat,
@@ -254,34 +254,6 @@ struct HistSplit {
   int64_t cstride = 0;
   const int4* cellinfo = nullptr;
 };
-
-// The previous level's split run by the leading blocks of a histogram pass (levels >= 2 of the exact fused
-// round): z-planes 0 .. nz - 1 are split blocks (node zb * gridDim.x + x of task y), the
-// remaining planes the histogram.  Split blocks come first in dispatch order; each runs gbdt_split's body
-// (its stores are write-through), drains them and adds 1 to its task's counter.  A histogram block of task
-// t polls that counter (one lane, agent-scope loads, bounded) until the task's nodes are all decided, then
-// reads the split arrays with agent-scope loads -- the "write-through stores + vmcnt(0) + relaxed arrival"
-// hand-off of HistSplit.  A task's next level starts when its own splits finish instead of at a launch
-// boundary; no block waits on another task.  The levels' chunk partials alternate between two buffer halves,
-// so this level's histogram never overwrites what the split blocks still read.  Counters are cumulative
-// over the fit (want = the running total); a timed-out poll raises err[0] (em_gbdt_fused_error).
-struct HistPre {
-  int on = 0, nz = 0, nodes = 0, level = 0, nchunks = 0, oneshot = 0, pscan = 0, NN = 0;
-  int want = 0;
-  int* ctr = nullptr;  // [T] cumulative arrivals
-  int* err = nullptr;  // set when a poll timed out (em_gbdt_fused_error)
-  const double* hist = nullptr;
-  int64_t cstride = 0;
-  double* G = nullptr;
-  double* H = nullptr;
-  int8_t* st = nullptr;
-  int16_t* fe = nullptr;
-  uint8_t* sb = nullptr;
-  float* gn = nullptr;
-  double lam = 0.0, mcw = 0.0;
-  const int4* cellinfo = nullptr;
-};
-constexpr int64_t PRE_SPIN_LIMIT = 1ll << 24;  // ~1 s of polling at s_sleep 1: a legitimate wait is microseconds
 
 // ---------------------------------------------------------------- K8 histogram (compact cells)
 // Cells: feature f owns bins [foff[f], foff[f+1]) of a compact axis of C = foff[F] cells (a one-hot
@@ -324,8 +296,8 @@ constexpr int HIST_EXACT_THREADS = GBDT_HIST_THREADS;
 #ifndef GBDT_HSPLIT_NPRE
 #define GBDT_HSPLIT_NPRE 4
 #endif
-// gbdt_hist's dynamic LDS ceiling: 160 KB less 2 KB for its static LDS (block_sum_waves, two split_body
-// instantiations: 1200 B); setting the attribute to the full 160 KB fails once the kernel has any static
+// gbdt_hist's dynamic LDS ceiling: 160 KB less 2 KB for its static LDS (block_sum_waves and the root split's
+// split_body: 672 B); setting the attribute to the full 160 KB fails once the kernel has any static
 // LDS (and leaves hipErrorInvalidValue as the last error, which the next launch check reports)
 constexpr int GBDT_HIST_MAX_DYN = 158 * 1024;
 constexpr int HIST_QBIN_LDS = 16 * 1024;         // fixed point: staged bin bytes per piece
@@ -344,7 +316,7 @@ gbdt_hist(const uint8_t* __restrict__ bins, const float* __restrict__ g, const f
           const int16_t* __restrict__ node, const int* __restrict__ foff, double* __restrict__ partial, int T, int n,
           int F, int C, int level, int chunk, int FT, int NTn, int P, int ldsC, int piece, int stage_rows,
           int16_t* __restrict__ node_out, const int8_t* __restrict__ pst, const int16_t* __restrict__ pfe,
-          const uint8_t* __restrict__ psb, int NN, HistUpdate hu, HistSplit hsp, HistPre pre) {
+          const uint8_t* __restrict__ psb, int NN, HistUpdate hu, HistSplit hsp) {
   // stage_rows > 0: each piece's bin rows are staged in LDS with 16-B loads (one round trip instead of
   // one per 8 rows of byte loads); the host sets it when a piece's rows fit (stage_rows * F <= 16 KB).
   // node_out != nullptr (level >= 1): the rows' nodes are the previous level's partition, applied here
@@ -354,34 +326,7 @@ gbdt_hist(const uint8_t* __restrict__ bins, const float* __restrict__ g, const f
   const int nodesL = 1 << level, first = nodesL - 1;
   GSTAMP(64 + 16 * level);
   const int c = blockIdx.x, t = blockIdx.y;
-  if (pre.on && (int)blockIdx.z < pre.nz) {  // a split block of the previous level (see HistPre)
-    const int nd = (int)blockIdx.z * (int)gridDim.x + c;
-    if (nd < pre.nodes) {
-      split_body<double, false, GBDT_HSPLIT_NPRE>(t * pre.nodes + nd, smem, pre.hist, pre.nchunks, pre.cstride, foff, T,
-                                                  F, C, pre.level, pre.NN, pre.G, pre.H, pre.st, pre.fe, pre.sb,
-                                                  pre.gn, pre.lam, pre.mcw, 0.0, SplitFinal(), pre.oneshot, pre.pscan,
-                                                  pre.cellinfo);
-      if (threadIdx.x == 0) {  // (thread 0 made every store of the split, all write-through)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(pre.ctr + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    return;
-  }
-  const int zb = (int)blockIdx.z - (pre.on ? pre.nz : 0);  // this block's plane of the histogram pass
-  if (pre.on) {  // the task's previous-level nodes must all be decided before their partition is applied
-    if (threadIdx.x == 0) {  // (the other threads load the split arrays after the barrier below)
-      int64_t spins = 0;
-      while (__hip_atomic_load(pre.ctr + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pre.want) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > PRE_SPIN_LIMIT) {
-          __hip_atomic_fetch_or(pre.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      }
-    }
-    __syncthreads();
-  }
+  const int zb = (int)blockIdx.z;
   if (hu.apply && zb >= hu.nz) {  // eval set es: round - 1's tree of task t on a chunk of its rows
     // (the set's fields picked with selects: a dynamic index into the by-value argument arrays would
     // copy them to scratch memory for every block of the launch)
@@ -424,16 +369,8 @@ gbdt_hist(const uint8_t* __restrict__ bins, const float* __restrict__ g, const f
   u32x4* sbw = reinterpret_cast<u32x4*>(reinterpret_cast<char*>(ptree) + (((size_t)npn * 4 + 15) & ~(size_t)15));
   if (npn) {
     const int64_t k0 = (int64_t)t * NN + pf;
-    for (int i = threadIdx.x; i < npn; i += blockDim.x) {
-      if (pre.on) {  // written in this launch by the split blocks (write-through): agent-scope loads
-        const int8_t a = __hip_atomic_load(pst + k0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint8_t b = __hip_atomic_load(psb + k0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int16_t e = __hip_atomic_load(pfe + k0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ptree[i] = (int32_t)(uint8_t)a | ((int32_t)b << 8) | ((int32_t)e << 16);
-      } else {
-        ptree[i] = (int32_t)(uint8_t)pst[k0 + i] | ((int32_t)psb[k0 + i] << 8) | ((int32_t)pfe[k0 + i] << 16);
-      }
-    }
+    for (int i = threadIdx.x; i < npn; i += blockDim.x)
+      ptree[i] = (int32_t)(uint8_t)pst[k0 + i] | ((int32_t)psb[k0 + i] << 8) | ((int32_t)pfe[k0 + i] << 16);
   }
   const int64_t base = (int64_t)t * n;
   const int nth = f1 - f0;
@@ -897,13 +834,14 @@ __global__ void gbdt_chunk_reduce(A* __restrict__ partial, int nchunks, int64_t 
 constexpr int SPLIT_FINAL_MAX_DEPTH = 8;
 constexpr int SPLIT_DIRECT_MAX_BINS = 32;  // direct candidate form up to this many bins per feature
 constexpr int EM_GBDT_SEPARATE = 1;  // em_gbdt_fit launch_flags: the separate launches instead of the fused round
-constexpr int EM_GBDT_PRESPLIT = 2;  // em_gbdt_fit launch_flags: splits inside the next level's histogram pass
 constexpr int SPLIT_ONESHOT_LDS = 48 * 1024;  // chunk partials staged at once up to this many bytes (+ the
                                               // finalize's <= 12 KB: within the default 64 KB)  // the fused finalize stages NN <= 511 nodes (23 B each) in LDS
 
 // One node's split (block vb = task * nodesL + node of the level), shared by the split launch and the
 // level-0 histogram pass that splits its task's root itself (COH: the chunk partials and the node's
-// status come from other workgroups of the same launch -- agent-scope loads, see HistSplit).
+// status come from other workgroups of the same launch -- agent-scope loads, see HistSplit).  Three
+// instantiations: <double, true, GBDT_HSPLIT_NPRE> in gbdt_hist, <double / long long, false, GBDT_SPLIT_NPRE>
+// in gbdt_split.  NPRE: one-shot partial loads in flight per thread.
 template <typename A, bool COH, int NPRE>
 EM_DEVICE void split_body(int vb, char* smem, const A* __restrict__ hist, int nchunks, int64_t cstride,
                           const int* __restrict__ foff, int T, int F, int C, int level, int NN, double* __restrict__ G,
@@ -952,7 +890,7 @@ EM_DEVICE void split_body(int vb, char* smem, const A* __restrict__ hist, int nc
   if (sti == 2) {  // block-uniform: an open node
     const A* hs = hs0;
     if (one) {
-      // every chunk's cells staged at once (32 loads per thread in flight: one round trip, where the
+      // every chunk's cells staged at once (NPRE loads per thread in flight: one round trip, where the
       // per-element chunk loop took 2-3), then folded in chunk order (== gbdt_chunk_reduce)
       A* stg = reinterpret_cast<A*>(smem);
       for (int b0 = threadIdx.x; b0 < tot; b0 += NPRE * blockDim.x) {
@@ -1701,15 +1639,13 @@ struct LevelHist {
   HistPartition partition = {};           // levels >= 1 of the fused round
   const HistUpdate* update = nullptr;     // level 0: the previous round's update and this round's start
   const HistSplit* root_split = nullptr;  // level 0: the root split by each task's last-arriving block
-  const HistPre* pre = nullptr;           // the previous level's split in the leading blocks
-  size_t min_lds = 0;                     // (root_split and pre run in the histogram's LDS)
+  size_t min_lds = 0;                     // (root_split runs in the histogram's LDS)
 };
 int launch_level_hist(const LevelHist& a, int* nchunks_out, hipStream_t stream) {
   const int level = a.level, T = a.T, n = a.n, F = a.F, C = a.foff_h[F], nodesL = 1 << level;
   const int *foff_h = a.foff_h, *foff_d = a.foff_d;
   const QuantAux* qa = a.qa;
   const HistUpdate* hu = a.update;
-  const HistPre* pre = a.pre;
   const double qscale = a.qscale;
   const bool quant = qscale != 0.0;
   const int64_t S = (int64_t)T * nodesL * C * 2;
@@ -1738,10 +1674,7 @@ int launch_level_hist(const LevelHist& a, int* nchunks_out, hipStream_t stream) 
     nchunks = pl.nchunks;
     // (hu: level 0 with one tile per (chunk, task); eval sets on extra z planes)
     if (hu && (quant || level != 0 || pl.nft * pl.ntn != 1)) return EM_ERR_ARG;
-    if (pre && (quant || hu || a.root_split)) return EM_ERR_ARG;
-    HistPre pr = pre ? *pre : HistPre();
-    if (pre) pr.nz = (pr.nodes + pl.nchunks - 1) / pl.nchunks;  // split planes in front of the histogram's
-    const dim3 grid(pl.nchunks, T, pr.nz + pl.nft * pl.ntn + (hu && hu->apply ? hu->evs.count : 0));
+    const dim3 grid(pl.nchunks, T, pl.nft * pl.ntn + (hu && hu->apply ? hu->evs.count : 0));
     if (quant)
       hipLaunchKernelGGL(gbdt_hist_q, grid, dim3(pl.threads), pl.lds, stream, a.bins, a.g, a.h, a.node, foff_d,
                          (const int*)nullptr, foff_d, qpart, T, n, F, F, C, level, pl.chunk, pl.FT, pl.NTn, pl.P,
@@ -1762,7 +1695,7 @@ int launch_level_hist(const LevelHist& a, int* nchunks_out, hipStream_t stream) 
       (void)attr;
       hipLaunchKernelGGL(gbdt_hist, grid, dim3(pl.threads), lds, stream, a.bins, a.g, a.h, a.node, foff_d, partial, T,
                          n, F, C, level, pl.chunk, pl.FT, pl.NTn, pl.P, pl.ldsC, pl.piece, stage, hp.node_out, hp.st,
-                         hp.fe, hp.sb, hp.NN, hu ? *hu : HistUpdate(), a.root_split ? *a.root_split : HistSplit(), pr);
+                         hp.fe, hp.sb, hp.NN, hu ? *hu : HistUpdate(), a.root_split ? *a.root_split : HistSplit());
     }
   }
   const bool split_folds = !a.fold && nchunks <= SPLIT_FOLD_MAX_CHUNKS && (int64_t)C * 16 <= SPLIT_FOLD_MAX_LDS;
@@ -1805,9 +1738,6 @@ int* zeroed_ints(ZeroedInts& z, int want) {
 int* task_counters(int T) { static ZeroedInts z; return zeroed_ints(z, T > 1024 ? T : 1024); }
 // the fused metric launches' arrival counter
 int* metric_counter() { static ZeroedInts z; return zeroed_ints(z, 16); }
-// raised by a histogram block whose HistPre poll timed out (the fit's trees are then invalid); read and cleared
-// by em_gbdt_fused_error
-int* fused_error_word() { static ZeroedInts z; return zeroed_ints(z, 16); }
 }  // namespace
 
 // ------------------------------------------------------------------ C ABI
@@ -1827,7 +1757,9 @@ EM_API int64_t em_gbdt_partial_doubles(int n, int T, int F, const int* foff, int
     if (v < 0) return -1;
     need = v > need ? v : need;
   }
-  // two halves (consecutive levels' partials, em_gbdt_fit's HistPre levels) while that stays small
+  // twice the planned need while that stays small: headroom that only the sparse fixed-point pass uses (its
+  // chunk cap in launch_level_hist is partial_doubles / S, and it wants 64-row chunks where partial_need plans
+  // 256-row ones); sizing it from the passes' own chunk counts is an open follow-up (docs/DESIGN.md section 7)
   return need <= (int64_t(1) << 24) ? 2 * need : need;
 }
 
@@ -1897,28 +1829,23 @@ EvalSets eval_sets(const EmGbdtEval* evals, int n_evals, int T, int* blocks = nu
 //                                                              in round r's update; the metrics every round, the
 //                                                              eval sets' by gbdt_predict_metric launches
 //   0           elementwise  <= 8   -         softmax    any   fused round, gbdt_round_start every round
-//   a fused round + PRESPLIT, depth >= 3, `partial` two levels wide: levels 1 .. depth - 2 split in the leading
-//                                                              blocks of the next level's pass (HistPre)
 //
 // hist_update also takes one histogram tile per (chunk, task) at level 0 and chunks x T <= 2^20; a fit without
 // either runs next_in_update with deferred metrics.  The fused round: the previous level's partition inside each
 // histogram pass (double-buffered nodes), the prune / leaves in the last level's split (last-arriving block per
 // task), the last partition in the update: 7 launches per depth-3 round instead of 13, bit-identical to the
 // separate launches.  Deferred metrics (<= 4 eval sets; metric_arrive_final with ctr == nullptr): every round's
-// per-block partials, reduced by gbdt_metric_rounds after the call's last round.  Presplit: bit-identical trees,
-// measured equal on the reference fit (profiles/r6/gbdt_presplit_ab.txt), so the split launches stay the default.
+// per-block partials, reduced by gbdt_metric_rounds after the call's last round.
 struct FitPlan {
   int NN = 0, C = 0, sets = 0;
   int64_t TN = 0;
   double qscale = 0.0, qinv = 0.0;
-  bool fuse = false, deferred = false, hist_update = false, next_in_update = false, presplit = false, fsplit = false;
+  bool fuse = false, deferred = false, hist_update = false, next_in_update = false, fsplit = false;
   int nch0 = 0;         // hist_update: the level-0 pass's chunks
   int64_t mstride = 0;  // doubles between the sets' deferred partials
-  int64_t half = 0;     // doubles of `partial` one level may use (presplit: levels alternate between two halves)
   SplitLds root;        // fsplit: the root split's LDS
   int* mctr = nullptr;  // arrival counter of the fused metric launches (re-armed by each)
   int* tctr = nullptr;  // fuse: [2 T] arrival counters of the fused finalize and the root split
-  int* perr = nullptr;  // presplit: the error word
 };
 
 bool make_plan(const FitArgs& a, FitPlan& p) {
@@ -1943,13 +1870,7 @@ bool make_plan(const FitArgs& a, FitPlan& p) {
   p.fsplit = p.hist_update && p.nch0 > 1 && p.nch0 <= SPLIT_FOLD_MAX_CHUNKS &&
              (int64_t)p.C * 16 <= SPLIT_FOLD_MAX_LDS && (int64_t)p.nch0 * p.C * 16 <= SPLIT_ONESHOT_LDS;
   if (p.fsplit) p.root = split_lds(p.nch0, p.C, p.NN, a.max_depth == 1);
-  int64_t pneed = 0;  // presplit: the partial buffer must hold two levels' partials (double-buffered halves)
-  for (int l = 0; l < a.max_depth; ++l) pneed = std::max(pneed, partial_need(l, a.n, a.T, a.F, a.foff_h));
-  p.presplit = (a.launch_flags & EM_GBDT_PRESPLIT) && p.fuse && a.max_depth >= 3 && pneed > 0 &&
-               a.partial_doubles >= 2 * pneed;
-  p.half = p.presplit ? (a.partial_doubles / 2) & ~(int64_t)1 : a.partial_doubles;
-  p.perr = p.presplit ? fused_error_word() : nullptr;
-  return !p.presplit || p.perr;
+  return true;
 }
 
 // The call's device scratch under one owner.  qmem outlives every launch of the call: freed after the stream
@@ -1960,11 +1881,9 @@ struct FitScratch {
   void* qmem = nullptr;
   int4* cellinfo = nullptr;  // [C] direct split candidates, or none
   double* mround = nullptr;  // deferred: [rounds][sets][mstride] metric partials
-  int* sctr = nullptr;       // presplit: [T] cumulative split arrivals of this fit
   explicit FitScratch(hipStream_t s) : stream(s) {}
   FitScratch(const FitScratch&) = delete;
   ~FitScratch() {
-    if (sctr) (void)hipFreeAsync(sctr, stream);
     if (mround) (void)hipFreeAsync(mround, stream);
     if (cellinfo) (void)hipFreeAsync(cellinfo, stream);
     if (qmem) {
@@ -2037,14 +1956,6 @@ struct RoundView {  // the tree arrays of one round, addressed from the host
   uint8_t* sb;
   float *lf, *gn, *cv;
 };
-// The only state carried from level to level and round to round (presplit): the previous level's split,
-// deferred into the next histogram pass, with its LDS size, and the arrivals per task so far in this call
-struct PreCarry {
-  HistPre pending;
-  size_t pending_lds = 0;
-  int cum = 0;
-};
-
 // round `rv.round`'s level-0 pass doing round - 1's update and the round's start
 HistUpdate level0_update(const FitArgs& a, const FitPlan& p, const FitScratch& sc, const RoundView& rv) {
   HistUpdate hu;
@@ -2076,14 +1987,13 @@ HistSplit root_split(const FitArgs& a, const FitPlan& p, const FitScratch& sc, c
 }
 
 // One level: the histogram pass (with whatever the plan folds into it) and the split launch, unless the pass
-// did the split (fsplit) or the next level's pass will (presplit: left in `pc`)
-int enqueue_level(const FitArgs& a, const FitPlan& p, const FitScratch& sc, const RoundView& rv, int level,
-                  PreCarry& pc) {
+// did the split (fsplit)
+int enqueue_level(const FitArgs& a, const FitPlan& p, const FitScratch& sc, const RoundView& rv, int level) {
   const int T = a.T, F = a.F, NN = p.NN, C = p.C, nodesL = 1 << level;
   hipStream_t s = a.stream;
   int16_t* nb[2] = {a.node, p.fuse ? a.node2 : a.node};
-  double* lpart = p.presplit ? a.partial + (level & 1) * p.half : a.partial;  // this level's partials
-  LevelHist lh{level, T, a.n, F, a.bins, a.g, a.h, a.node, a.foff_h, a.foff_d, lpart, p.half, false, p.qscale};
+  LevelHist lh{level, T, a.n, F, a.bins, a.g, a.h, a.node, a.foff_h, a.foff_d, a.partial, a.partial_doubles, false,
+               p.qscale};
   lh.qa = sc.qa.nb ? &sc.qa : nullptr;
   if (p.fuse && level >= 1) {
     lh.node = nb[(level - 1) & 1];
@@ -2094,39 +2004,24 @@ int enqueue_level(const FitArgs& a, const FitPlan& p, const FitScratch& sc, cons
   const HistSplit hsp = fsplit ? root_split(a, p, sc, rv) : HistSplit();
   if (hu.on) lh.update = &hu;
   if (hsp.on) lh.root_split = &hsp, lh.min_lds = p.root.bytes;
-  if (pc.pending.on) {
-    pc.pending.want = pc.cum += pc.pending.nodes;
-    lh.pre = &pc.pending, lh.min_lds = pc.pending_lds;
-  }
   int nch = 1;
   const int rc = launch_level_hist(lh, &nch, s);
-  pc.pending = HistPre();
   if (rc) return rc;
   if (fsplit) return 0;  // (split done by the pass itself)
   const int sth = (F >= 256 || nch > 1) ? 256 : ((F + 63) / 64) * 64;
   const int64_t cstride = (int64_t)T * nodesL * C * 2;
   const bool last = p.fuse && level == a.max_depth - 1;
   const SplitLds sl = split_lds(nch, C, NN, last);
-  if (p.presplit && level >= 1 && level + 1 < a.max_depth) {  // runs in the next level's histogram pass
-    HistPre& pre = pc.pending;
-    pre.on = 1, pre.nodes = nodesL, pre.level = level, pre.NN = NN;
-    pre.hist = lpart, pre.nchunks = nch, pre.cstride = cstride, pre.oneshot = sl.oneshot, pre.pscan = sl.pscan;
-    pre.ctr = sc.sctr, pre.err = p.perr;
-    pre.G = a.Gs, pre.H = a.Hs, pre.lam = (double)a.lam, pre.mcw = (double)a.mcw, pre.cellinfo = sc.cellinfo;
-    pre.st = rv.st, pre.fe = rv.fe, pre.sb = rv.sb, pre.gn = rv.gn;
-    pc.pending_lds = sl.bytes;
-    return 0;
-  }
   const SplitFinal fin = last ? split_final(a, p, rv) : SplitFinal();
   if (a.quant_bits)
     hipLaunchKernelGGL(gbdt_split<long long>, dim3(T * nodesL), dim3(sth), sl.bytes, s,
-                       reinterpret_cast<const long long*>(lpart), nch, cstride, a.foff_d, T, F, C, level, NN, a.Gs,
+                       reinterpret_cast<const long long*>(a.partial), nch, cstride, a.foff_d, T, F, C, level, NN, a.Gs,
                        a.Hs, rv.st, rv.fe, rv.sb, rv.gn, (double)a.lam, (double)a.mcw, p.qinv, fin, sl.oneshot,
                        sl.pscan, sc.cellinfo);
   else
-    hipLaunchKernelGGL(gbdt_split<double>, dim3(T * nodesL), dim3(sth), sl.bytes, s, lpart, nch, cstride, a.foff_d,
-                       T, F, C, level, NN, a.Gs, a.Hs, rv.st, rv.fe, rv.sb, rv.gn, (double)a.lam, (double)a.mcw, 0.0,
-                       fin, sl.oneshot, sl.pscan, sc.cellinfo);
+    hipLaunchKernelGGL(gbdt_split<double>, dim3(T * nodesL), dim3(sth), sl.bytes, s, a.partial, nch, cstride,
+                       a.foff_d, T, F, C, level, NN, a.Gs, a.Hs, rv.st, rv.fe, rv.sb, rv.gn, (double)a.lam,
+                       (double)a.mcw, 0.0, fin, sl.oneshot, sl.pscan, sc.cellinfo);
   if (!p.fuse)
     hipLaunchKernelGGL(gbdt_partition, dim3(grid_for(p.TN)), dim3(256), 0, s, a.bins, a.node, T, a.n, F, NN, rv.st,
                        rv.fe, rv.sb, level);
@@ -2186,7 +2081,7 @@ int enqueue_round_metrics(const FitArgs& a, const FitPlan& p, const FitScratch& 
 }
 
 // One round's kernel sequence
-int enqueue_round(const FitArgs& a, const FitPlan& p, const FitScratch& sc, int round, PreCarry& pc) {
+int enqueue_round(const FitArgs& a, const FitPlan& p, const FitScratch& sc, int round) {
   const int T = a.T, NN = p.NN;
   const int64_t ro = (int64_t)round * T * NN;
   const RoundView rv{round, a.status + ro, a.feat + ro, a.sbin + ro, a.leaf + ro, a.gainv + ro, a.cover + ro};
@@ -2196,7 +2091,7 @@ int enqueue_round(const FitArgs& a, const FitPlan& p, const FitScratch& sc, int 
                        0, s, rv.st, rv.fe, rv.sb, rv.gn, T * NN, NN, a.margin, a.Y, a.g, a.h, a.node, T, a.n, a.obj,
                        a.subsample, a.seed, round);
   for (int level = 0; level < a.max_depth; ++level)
-    if (int rc = enqueue_level(a, p, sc, rv, level, pc)) return rc;
+    if (int rc = enqueue_level(a, p, sc, rv, level)) return rc;
   if (!p.fuse)
     hipLaunchKernelGGL(gbdt_finalize, dim3((T + 63) / 64), dim3(64), 0, s, T, NN, a.max_depth, rv.st, rv.fe, rv.gn,
                        a.Gs, a.Hs, rv.lf, rv.cv, (double)a.lam, a.gamma, (double)a.eta);
@@ -2210,7 +2105,7 @@ int enqueue_round(const FitArgs& a, const FitPlan& p, const FitScratch& sc, int 
 // for the kernels); feature f has foff[f+1]-foff[f] bins.
 // scratch: g, h [T][n]; node, node2 int16 [T][n]; partial (em_gbdt_partial_doubles); G, H [T][NN]; mpart double[5 * 4096]
 // hist_out: float [R][1 + n_evals] (metric of train + each eval set after each round)
-// launch_flags: EM_GBDT_SEPARATE, EM_GBDT_PRESPLIT (the only switches of the round form: FitPlan)
+// launch_flags: EM_GBDT_SEPARATE (the only switch of the round form: FitPlan); any other bit is an argument error
 EM_API int em_gbdt_fit(const uint8_t* bins, const float* Y, int n, int F, const int* foff_h, const int* foff_d, int T,
                        float* margin, const EmGbdtEval* evals, int n_evals, int r0, int r1, int max_depth, int obj,
                        int metric, float eta, float lam, float gamma, float mcw, float subsample, uint32_t seed,
@@ -2219,7 +2114,8 @@ EM_API int em_gbdt_fit(const uint8_t* bins, const float* Y, int n, int F, const 
                        float* leaf, float* gainv, float* cover, float* hist_out, int quant_bits, int launch_flags,
                        hipStream_t stream) {
   if (!bins || !Y || !margin || n <= 0 || F <= 0 || !valid_foff(foff_h, F) || !foff_d || T <= 0 || max_depth < 1 ||
-      max_depth > 12 || r0 < 0 || r1 < r0 || quant_bits < 0 || quant_bits > 61)
+      max_depth > 12 || r0 < 0 || r1 < r0 || quant_bits < 0 || quant_bits > 61 ||
+      (launch_flags & ~EM_GBDT_SEPARATE))
     return EM_ERR_ARG;
   // fixed-point histograms (quant_bits = s > 0): the caller guarantees |g|, |h| <= 1 and n < 2^(61-s),
   // so every per-cell and per-node sum of q = rint(x * 2^s) stays below 2^61 in magnitude
@@ -2235,13 +2131,8 @@ EM_API int em_gbdt_fit(const uint8_t* bins, const float* Y, int n, int F, const 
   if (p.deferred && hipMallocAsync(reinterpret_cast<void**>(&sc.mround),
                                    (size_t)(r1 - r0) * p.sets * p.mstride * sizeof(double), stream) != hipSuccess)
     return EM_ERR_ARG;
-  const size_t tb = (size_t)T * sizeof(int);
-  if (p.presplit && (hipMallocAsync(reinterpret_cast<void**>(&sc.sctr), tb, stream) != hipSuccess ||
-                     hipMemsetAsync(sc.sctr, 0, tb, stream) != hipSuccess))
-    return EM_ERR_ARG;
-  PreCarry pc;
   for (int round = r0; round < r1; ++round)
-    if (int rc = enqueue_round(a, p, sc, round, pc)) return rc;
+    if (int rc = enqueue_round(a, p, sc, round)) return rc;
   if (p.deferred) {  // every round's metric partials -> hist_out
     MetricRounds mr{};
     mr.count[0] = p.TN;
@@ -2260,18 +2151,6 @@ EM_API int em_gbdt_fit(const uint8_t* bins, const float* Y, int n, int F, const 
     EM_CHECK_LAUNCH();
   }
   return 0;
-}
-
-// 1 if a fused-level poll timed out since the last call (the trees of that fit are invalid), else 0;
-// synchronises the device and clears the word
-EM_API int em_gbdt_fused_error() {
-  int* w = fused_error_word();
-  if (!w) return -1;
-  int v = 0;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, w, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-    return -1;
-  if (v) (void)hipMemset(w, 0, sizeof(int));
-  return v;
 }
 
 // GBDT_STAMPS builds: the 256 phase stamps (100 MHz ticks) and the matching 256 shader-clock counts

@@ -242,15 +242,13 @@ def test_hip_fused_round_bit_identical(obj):
               eval_metric="logloss" if obj == "reg:logistic" else "rmse", subsample=0.8, backend="hip")
     ev = {"test": (X[m:], Y[m:])}
     fits = {}
-    for name in ("fused", "separate", "presplit"):
+    for name in ("fused", "separate"):
         g = G.GBDT(**kw)
         g.separate_launches = name == "separate"
-        g.presplit_levels = name == "presplit"  # level L's split inside level L + 1's histogram pass
         fits[name] = g.fit(X[:m], Y[:m], evals=ev)
     a, b = fits["fused"], fits["separate"]
     for k in ("status", "feat", "sbin", "leaf", "gain", "cover"):
         assert np.array_equal(getattr(a.trees, k), getattr(b.trees, k)), k
-        assert np.array_equal(getattr(fits["presplit"].trees, k), getattr(b.trees, k)), k
     # (the fused rounds sum the per-round metric terms grouped by histogram chunk, the separate launches by
     # update block: the same terms, summed in another order)
     assert len(a.history) == len(b.history)
@@ -277,6 +275,9 @@ def test_native_hist_plan_bounds():
         return N.query("em_gbdt_partial_doubles", n, T, F, off.ctypes.data, D)
 
     assert 0 < need(928, 62, 66, 3, 3) <= 1 << 27
+    # the planner's size, pinned: 2 x (4 chunks x 62 tasks x 4 nodes x 198 cells x 2), and a 2-chunk depth-1 shape
+    assert need(928, 62, 66, 3, 3) == 785664
+    assert need(257, 1, 4, 3, 1) == 96
     assert 0 < need(183500, 62, 66, 7, 3) <= 1 << 27
     assert 0 < need(100000, 62, 66, 256, 6) <= 1 << 27
     assert need(100000, 62, 66, 256, 12) == -1

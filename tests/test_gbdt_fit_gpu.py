@@ -21,7 +21,7 @@ from euromillioner_amd.models import gbdt as G
 
 pytestmark = pytest.mark.gpu
 
-DRIVERS = ("default", "separate", "presplit")
+DRIVERS = ("default", "separate")
 TREE_ARRAYS = ("status", "feat", "sbin", "leaf", "gain", "cover")
 _fits: dict = {}
 
@@ -29,7 +29,6 @@ _fits: dict = {}
 def _new(objective, driver="default", backend="hip", **kw):
     g = G.GBDT(objective=objective, backend=backend, **kw)
     g.separate_launches = driver == "separate"
-    g.presplit_levels = driver == "presplit"
     return g
 
 
@@ -257,28 +256,21 @@ def test_62_tasks():
     _check(m, "t62", "9 T = 62")
 
 
-# ----------------------------------------------------------------------------- 10. what the presplit driver carries
-def test_presplit_depth_6():
-    """Levels 1 to 4 are pending splits, their partials alternating between the two halves of the partial
-    buffer (depth 3 has one pending level): the default driver's trees, bit for bit."""
-    m, base = _hip("depth-6", "presplit"), _hip("depth-6")
-    for k in TREE_ARRAYS:
-        assert np.array_equal(getattr(m.trees, k), getattr(base.trees, k)), k
-    _check(m, "depth-6", "10 depth 6 presplit")
-
-
-def test_presplit_chunked_calls(monkeypatch):
-    """rounds_per_call = 3 over 7 rounds on the presplit driver: the arrival total the histogram blocks wait for
-    restarts with each call, beside that call's zeroed counters."""
+# ----------------------------------------------------------------------------- 10. launch flags
+def test_unknown_launch_flag_is_rejected(monkeypatch):
+    """``em_gbdt_fit`` knows one launch flag (1, the separate launches): a call with bit 2 set fails in the
+    argument check, before any launch, and ``fit`` raises instead of running some other driver."""
     from euromillioner_amd.models import gbdt_hip
 
-    case = "sub-0.8-rounds7"
-    whole = _hip(case)
-    dn, objective, kw = K.CASES[case]
+    call = gbdt_hip.N.call
+
+    def with_flag_2(name, *args):
+        if name == "em_gbdt_fit":
+            args = args[:-2] + (args[-2] | 2,) + args[-1:]
+        return call(name, *args)
+
+    dn, objective, kw = K.CASES["std-logistic"]
     X, Y, _ = K.data(dn)
-    monkeypatch.setattr(gbdt_hip, "fit", functools.partial(gbdt_hip.fit, rounds_per_call=3))
-    m = _new(objective, "presplit", **kw).fit(X, Y)
-    assert m.backend_used == "hip"
-    for k in TREE_ARRAYS:
-        assert np.array_equal(getattr(m.trees, k), getattr(whole.trees, k)), k
-    _check(m, case, "10 sub-0.8-rounds7 presplit rounds_per_call 3")
+    monkeypatch.setattr(gbdt_hip.N, "call", with_flag_2)
+    with pytest.raises(ValueError):
+        _new(objective, **kw).fit(X, Y)

@@ -1,7 +1,7 @@
 """The GBDT watch-list metrics (K13 and its fused forms) and ``em_gbdt_predict`` (K11) against the fp64
 reference of tests/_gbdt_ref.py: every round, every watch set and the train metric, for every metric and
 objective on every driver path (fused round with the update inside the next level-0 histogram pass, separate
-launches, presplit levels, more than four watch sets, chunked ``em_gbdt_fit`` calls, fixed-point histograms,
+launches, more than four watch sets, chunked ``em_gbdt_fit`` calls, fixed-point histograms,
 element counts past the 4096-block grid cap, the one-rank data-parallel path).
 
 The reference is built from the fitted model's own trees and cuts, so a metric failure cannot hide behind a
@@ -19,7 +19,7 @@ from euromillioner_amd.models import gbdt as G
 
 pytestmark = pytest.mark.gpu
 
-DRIVERS = ("default", "separate", "presplit")
+DRIVERS = ("default", "separate")
 TREE_ARRAYS = ("status", "feat", "sbin", "leaf", "gain", "cover")
 _models: dict = {}
 
@@ -37,7 +37,6 @@ def _large():
 def _new(objective, metric, driver="default", **kw):
     g = G.GBDT(objective=objective, eval_metric=metric, backend="hip", **dict(D.KW, **kw))
     g.separate_launches = driver == "separate"
-    g.presplit_levels = driver == "presplit"
     return g
 
 

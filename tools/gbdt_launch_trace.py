@@ -5,12 +5,15 @@ csrc/gbdt.hip), for comparing two builds of the driver: a host-side change must 
     rocprofv3 --kernel-trace --output-format csv -d A -o run -- python tools/gbdt_launch_trace.py run
     EUROM_NATIVE_LIB=<other build> rocprofv3 --kernel-trace --output-format csv -d B -o run -- \
         python tools/gbdt_launch_trace.py run
-    python tools/gbdt_launch_trace.py compare A B
+    python tools/gbdt_launch_trace.py compare A B [KERNEL ...]
 
 ``run`` fits the cases in one process (each printed with a hash of its six tree arrays) and puts a marker -- three
 one-block ``gbdt_init_margin`` launches -- in front of each.  ``compare`` reads the two traces, keeps the ``gbdt_``
-kernels in dispatch order as (name, grid, workgroup, LDS bytes), splits them at the markers and prints the
-dispatch count per case and "identical" or the first difference; exit status 1 if any case differs."""
+kernels in dispatch order as (name without its parameter list, grid, workgroup, LDS bytes), splits them at the
+markers and prints the dispatch count per case and "identical" or the first difference; exit status 1 if any case
+differs.  The trace's LDS bytes are the kernel's static LDS rounded up to 512 (the launch's dynamic LDS is not in
+it): for a KERNEL named after the two directories, whose device code changed between the builds, that column is
+left out of the comparison and its (A, B) values are printed instead."""
 from __future__ import annotations
 
 import csv
@@ -19,6 +22,7 @@ import glob
 import hashlib
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,14 +30,13 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 # (label, case of tests/_gbdt_fit_cases.py, driver, watch sets, eval_metric, rounds_per_call)
 CASES = [
-    *[(f"std-logistic 2 sets {d}", "std-logistic", d, 2, None, None) for d in ("default", "separate", "presplit")],
+    *[(f"std-logistic 2 sets {d}", "std-logistic", d, 2, None, None) for d in ("default", "separate")],
     ("std-softprob", "std-softprob", "default", 0, None, None),
     ("softprob merror 2 sets", "std-softprob", "default", 2, "merror", None),
     ("std-logistic 5 sets", "std-logistic", "default", 5, None, None),
     ("quant-mixed-logistic", "quant-mixed-logistic", "default", 0, None, None),
     ("quant-cont-logistic", "quant-cont-logistic", "default", 0, None, None),
     ("depth-1", "depth-1", "default", 0, None, None),
-    ("depth-6 presplit", "depth-6", "presplit", 0, None, None),
     ("depth-9", "depth-9", "default", 0, None, None),
     ("rows-257", "rows-257", "default", 0, None, None),
     ("rows-8448", "rows-8448", "default", 0, None, None),
@@ -64,7 +67,7 @@ def run():
             assert sets["train"][0] is X or np.array_equal(sets["train"][0], X)
             evals = D.watch(sets, n_sets)
         g = G.GBDT(objective=objective, backend="hip", **dict(kw, **({"eval_metric": metric} if metric else {})))
-        g.separate_launches, g.presplit_levels = driver == "separate", driver == "presplit"
+        g.separate_launches = driver == "separate"
         for _ in range(3):
             N.call("em_gbdt_init_margin", mark.data_ptr(), 1, 0.0, N.stream_handle(dev))
         gbdt_hip.fit = functools.partial(whole_fit, rounds_per_call=per_call) if per_call else whole_fit
@@ -86,8 +89,10 @@ def dispatches(trace_dir):
     rows = list(csv.DictReader(open(paths[0])))
     rows.sort(key=lambda r: int(r["Dispatch_Id"]))
     dims = lambda r, stem: tuple(int(r[k]) for k in sorted(r) if k.startswith(stem))  # noqa: E731
-    return [(r["Kernel_Name"], dims(r, "Grid_Size"), dims(r, "Workgroup_Size"), int(r["LDS_Block_Size"]))
-            for r in rows if "gbdt_" in r["Kernel_Name"]]
+    # (the kernel's name with its template arguments, without the parameter list: a build that drops a kernel
+    # parameter still compares)
+    return [(m.group(0), dims(r, "Grid_Size"), dims(r, "Workgroup_Size"), int(r["LDS_Block_Size"]))
+            for r in rows for m in [re.search(r"gbdt_\w+(<[^>]*>)?", r["Kernel_Name"])] if m]
 
 
 def per_case(seq):
@@ -108,8 +113,13 @@ def per_case(seq):
     return out
 
 
-def compare(dir_a, dir_b):
-    a, b = per_case(dispatches(dir_a)), per_case(dispatches(dir_b))
+def compare(dir_a, dir_b, lds_changed=()):
+    sa, sb = dispatches(dir_a), dispatches(dir_b)
+    if lds_changed:
+        pairs = sorted({(x[0], x[3], y[3]) for x, y in zip(sa, sb) if x[0] == y[0] and x[0] in lds_changed})
+        print("static LDS not compared (A, B):", ", ".join(f"{k} ({la}, {lb})" for k, la, lb in pairs))
+        sa, sb = ([d[:3] + (None,) if d[0] in lds_changed else d for d in s] for s in (sa, sb))
+    a, b = per_case(sa), per_case(sb)
     bad = len(a) != len(CASES) or len(b) != len(CASES)
     if bad:
         print(f"cases: {len(a)} and {len(b)} traced, {len(CASES)} expected")
@@ -132,7 +142,7 @@ def compare(dir_a, dir_b):
 if __name__ == "__main__":
     if len(sys.argv) == 2 and sys.argv[1] == "run":
         run()
-    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    elif len(sys.argv) >= 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[4:]))
     else:
         raise SystemExit(__doc__)
