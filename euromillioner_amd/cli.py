@@ -7,6 +7,7 @@ runs the whole pipeline (``Main.java:35``).  Here:
     euromillioner run [flags]          # same, with flags (reference defaults)
     euromillioner train --model mlp    # 62->128->62 MLP on the fused HIP path (DP via torchrun)
     euromillioner train --model mlp-wide | rf | gbdt
+    euromillioner train --model rf --data-source device --n-draws 700000   # draws generated on the GPU, never on the host
     euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv] [--tickets 5 --temperature 1.0]
     euromillioner backtest --ckpt model.zip --tickets 16   # prize tiers of sampled tickets on the validation split
     euromillioner explain --ckpt model.json [--top 3]      # which of the last draw's numbers push each GBDT pick (TreeSHAP)
@@ -39,7 +40,8 @@ _FLAGS = {
     "--eta": "gbdt.eta", "--max-depth": "gbdt.max_depth", "--objective": "gbdt.objective",
     "--subsample": "gbdt.subsample", "--nthread": "gbdt.nthread", "--gamma": "gbdt.gamma",
     "--eval-metric": "gbdt.eval_metric", "--nround": "gbdt.nround", "--lambda": "gbdt.reg_lambda",
-    "--min-child-weight": "gbdt.min_child_weight", "--num-class": "gbdt.num_class", "--target": "gbdt.target", "--max-bin": "gbdt.max_bin",
+    "--min-child-weight": "gbdt.min_child_weight", "--num-class": "gbdt.num_class", "--target": "gbdt.target",
+    "--gbdt-target": "gbdt.target", "--max-bin": "gbdt.max_bin",
     "--trees": "rf.n_trees", "--rf-max-depth": "rf.max_depth", "--min-samples-leaf": "rf.min_samples_leaf",
     "--feature-subset": "rf.feature_subset", "--oob": "rf.oob",
     "--hidden": "mlp.hidden", "--activation": "mlp.activation", "--loss": "mlp.loss", "--lr": "mlp.lr",
@@ -136,6 +138,10 @@ def main(argv=None) -> int:
         except ValueError as e:
             log.error(f"invalid configuration: {e}")
             return 2
+        if world > 1 and cfg.data.source == "device" and (a.cmd == "run" or cfg.model in ("rf", "gbdt")):
+            log.error("invalid configuration: data.source=device trains the tree models in a single process "
+                      "(no --dp, no torchrun)")
+            return 2
         if must_spawn:
             log.info(f"launching {world} ranks (127.0.0.1 rendezvous)"
                      + (f", up to {cfg.dist.max_restarts} restart(s)" if cfg.dist.max_restarts else ""))
@@ -168,6 +174,9 @@ def main(argv=None) -> int:
         else:
             ap.print_help()
             return 2
+    except C.ConfigError as e:
+        log.error(f"invalid configuration: {e}")
+        return 2
     except (FileNotFoundError, ValueError) as e:
         log.error(f"data/config error: {e}")
         log.debug(traceback.format_exc())

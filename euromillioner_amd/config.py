@@ -34,6 +34,11 @@ REFERENCE_URL = ("http://portalseven.com/lottery/euromillions_winning_numbers.js
 REFERENCE_TABLE_CLASS = "table table-bordered table-condensed table-striped text-center table-hover"  # Main.java:62
 
 
+class ConfigError(ValueError):
+    """A combination of settings that cannot run (found once the run has started, e.g. against the free device
+    memory).  The CLI reports it like any configuration error: exit code 2."""
+
+
 @dataclasses.dataclass
 class DataConfig:
     source: str = "synthetic"  # synthetic | csv | html | reference-csv | device (generated on the GPU)

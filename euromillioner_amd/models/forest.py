@@ -174,6 +174,30 @@ class RandomForest:
         self.feat, self.value, self.gain, self.cover = feat, value, gain, cover
         return self
 
+    def fit_draw_masks(self, masks, lags: int = 1, rows: tuple[int, int] | None = None, group=None):
+        """Fit on device draw masks (int64 [n] on the GPU): samples ``rows = (a, b)`` of the lag-window numbering of
+        ``ops.tree_inputs.rf_rows`` (sample ``s``: draws ``s .. s+lags-1`` -> draw ``s+lags``; default: all of
+        them).  The packed rows are built on the device and never leave it; the trees equal :meth:`fit` on the
+        host rows ``draw_features`` builds from the same draws.  Single process."""
+        if group is not None:
+            raise ValueError("fit_draw_masks is single-process (no process group)")
+        if self.device == "cpu":
+            raise ValueError("fit_draw_masks runs on the GPU (device=cpu was asked for)")
+        from ..ops import forest as K
+        from ..ops import tree_inputs as TI
+
+        a, b = (0, None) if rows is None else (int(rows[0]), int(rows[1]))
+        X, Y, F = TI.rf_rows(masks, lags, first=a, count=None if b is None else b - a)
+        self.F = int(F)
+        self.k = n_candidates(self.feature_subset, F)
+        self.n_train = int(X.shape[0])
+        self.tree_start = 0
+        self.backend_used = "hip"
+        self.feat, self.value, self.gain, self.cover = K.fit(
+            X, Y, self.F, 0, self.n_trees, self.max_depth, self.k, self.min_samples_leaf, self.bootstrap, self.seed,
+            device=masks.device)
+        return self
+
     def _fit_numpy(self, X, Y, trees):
         from .forest_oracle import grow_forest_numpy
 

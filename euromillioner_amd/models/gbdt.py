@@ -71,6 +71,13 @@ def make_cuts(X: np.ndarray, max_bin: int = 256) -> list[np.ndarray]:
     return cuts
 
 
+def cuts_from_bit_counts(counts, S: int) -> list[np.ndarray]:
+    """:func:`make_cuts` of a 0/1 matrix from its column sums alone: ``counts[f]`` ones among ``S`` rows.  A column
+    that takes both values (``0 < count < S``) has the one cut 0.5, a constant column none."""
+    S = int(S)
+    return [np.array([0.5]) if 0 < int(c) < S else np.zeros(0, dtype=np.float64) for c in counts]
+
+
 class _DP:
     """C4 helper: histogram / sum all-reduce for data-parallel boosting (every rank holds a row
     shard; identical global sums give identical splits, so trees need no broadcast)."""
@@ -531,6 +538,78 @@ class GBDT:
                 self.trees, self.history = self._fit_numpy(X, bins, nbins, Y, evals, dp=dp)
         self.trees.set_split_values(self.cuts)
         return self
+
+    # ------------------------------------------------------------------ device-resident draws
+    @staticmethod
+    def _mask_rows(masks, rows, what: str) -> tuple[int, int]:
+        a, b = (int(v) for v in rows)
+        n = int(masks.shape[0])
+        if not 0 <= a < b or b + 1 > n:
+            raise ValueError(f"{what}: samples [{a}, {b}) must satisfy 0 <= a < b <= {n - 1} (sample s reads draws s "
+                             f"and s + 1 of the {n} masks)")
+        if b - a >= 2 ** 31 - 1:
+            raise ValueError(f"{what}: at most 2^31-2 rows")
+        return a, b
+
+    def fit_draw_masks(self, masks, rows, evals: dict | None = None, group=None):
+        """The next-draw task straight from device masks (int64 [n] on the GPU, ``ops.tree_inputs``): sample ``s``
+        of ``rows = (a, b)`` has the 62 bits of draw ``s`` as features and the 62 bits of draw ``s + 1`` as the
+        targets of 62 boosters.  ``evals = {"name": (a, b), ...}`` are sample ranges of the same masks; one that
+        names the training rows shares their bins and targets.  Equal, tree for tree and metric for metric, to
+        :meth:`fit` on the host matrices ``multi_hot`` builds from the same draws (HIP backend).  Single process;
+        ``multi:*`` objectives have no one-label-per-row form here."""
+        if group is not None:
+            raise ValueError("fit_draw_masks is single-process (no data-parallel group)")
+        if self.objective in MULTI:
+            raise ValueError(f"fit_draw_masks trains 62 binary boosters; objective {self.objective} does not apply")
+        if self.backend == "numpy":
+            raise ValueError("fit_draw_masks runs on the HIP engine (backend numpy was asked for)")
+        from ..ops import tree_inputs as TI
+        from . import gbdt_hip
+
+        a, b = self._mask_rows(masks, rows, "fit_draw_masks")
+        ev_rows = {name: self._mask_rows(masks, r, f"fit_draw_masks eval {name!r}") for name, r in (evals or {}).items()}
+        counts = TI.bit_counts(masks, a, b)  # the training rows' input draws
+        self.cuts = cuts_from_bit_counts(counts[:TI.NF], b - a)
+        self.num_feature = self.n_tasks = TI.NF
+        varied = TI.varied_mask(counts, b - a)
+        d_bins, d_Y = TI.gbdt_draw_inputs(masks, a, b - a, varied)
+        ev_sets = []
+        for name, (ea, eb) in ev_rows.items():
+            if (ea, eb) == (a, b):  # the training rows: their bins and targets, a margin of its own
+                ev_sets.append((name, d_bins, d_Y))
+            else:
+                ev_sets.append((name, *TI.gbdt_draw_inputs(masks, ea, eb - ea, varied)))
+        self.train_history = []
+        self.backend_used = "hip"
+        self.trees, self.history = gbdt_hip._fit_device(self, d_bins, d_Y, ev_sets)
+        self.trees.set_split_values(self.cuts)
+        return self
+
+    def predict_margin_draw_masks(self, masks, rows):
+        """float32 [S, 64] on the device: the margins of samples ``rows = (a, b)`` of device masks (features: the
+        bits of draw ``s``), booster ``t`` in column ``t`` and zeros in columns 62-63, the logit rows
+        ``ops.fused_mlp.draw_metrics(..., loss="bce")`` and ``ops.tickets.draw_tickets`` take.  Bit-equal to
+        :meth:`predict_margin` (HIP) on the host rows.  Needs a next-draw model over the 62 draw bits."""
+        from ..ops import tree_inputs as TI
+        from . import gbdt_hip
+
+        if self.trees is None:
+            raise ValueError("the model is not fitted")
+        nf = len(self.cuts) if self.cuts is not None else self.num_feature
+        if nf != TI.NF or self.n_tasks != TI.NF:
+            raise ValueError(f"predict_margin_draw_masks needs 62 features and 62 boosters, the model has {nf} and "
+                             f"{self.n_tasks}")
+        a, b = (int(v) for v in rows)
+        if self.cuts is not None:
+            varied = sum(1 << f for f, c in enumerate(self.cuts) if len(c))
+        else:  # a loaded model: every split must be the 0 | 1 split (sbin 0), constant columns are never split on
+            tr = self.trees
+            if np.any(tr.split_value[tr.status == 1] != 0.5):
+                raise ValueError("predict_margin_draw_masks needs a model whose splits are all at 0.5")
+            varied = (1 << TI.NF) - 1
+        d_bins, _ = TI.gbdt_draw_inputs(masks, a, b - a, varied, targets=False)
+        return gbdt_hip.predict_margin_rows(self, d_bins)
 
     def _fit_numpy(self, X, bins, nbins, Y, evals, dp=None):
         """Oracle, vectorised over tasks and nodes: per level one GEMM of the one-hot bin matrix

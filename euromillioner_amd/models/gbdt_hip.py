@@ -71,30 +71,60 @@ class _Cells:
 def fit(model, X, bins, nbins, Y, evals, rounds_per_call: int = 500, dp=None):
     """Returns (trees, history).  ``model.train_history`` gets the eval metric on the training rows after
     each round (R floats, column 0 of the driver's per-round metric table).  The data-parallel path does
-    not compute that column: there ``train_history`` stays empty."""
+    not compute that column: there ``train_history`` stays empty.
+
+    This half bins and uploads the host arrays; :func:`_fit_device` runs the rounds on what it uploaded."""
     dev = _dev()
-    n, F = bins.shape
-    T = Y.shape[1]
-    R, D = model.nround, model.max_depth
-    NN = 2 ** (D + 1) - 1
-    cells = _Cells(model.cuts, dev)
     d_bins = torch.from_numpy(np.ascontiguousarray(bins, dtype=np.uint8)).to(dev)
     d_Y = torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float32)).to(dev)
-    margin = torch.empty(T * n, dtype=torch.float32, device=dev)
-    stream = N.stream_handle(dev)
-    N.call("em_gbdt_init_margin", margin.data_ptr(), T * n, float(model.base_margin), stream)
-    ev_names = list(evals.keys())
-    ev_keep = []
-    ev_structs = (_Eval * max(1, len(ev_names)))()
-    for i, name in enumerate(ev_names):
-        ex, ey = evals[name]
+    ev_sets = []
+    for name, (ex, ey) in evals.items():
         eb = apply_bins(np.asarray(ex, np.float64), model.cuts)
         db = torch.from_numpy(np.ascontiguousarray(eb, dtype=np.uint8)).to(dev)
         dy = torch.from_numpy(np.ascontiguousarray(np.asarray(ey, np.float32).reshape(len(ex), -1))).to(dev)
-        em = torch.empty(T * len(ex), dtype=torch.float32, device=dev)
+        ev_sets.append((name, db, dy))
+    return _fit_device(model, d_bins, d_Y, ev_sets, rounds_per_call, dp)
+
+
+def fit_buffer_bytes(n: int, T: int, F: int, cuts, max_depth: int, nround: int, eval_rows=()) -> int:
+    """Device bytes :func:`_fit_device` allocates around ``n`` rows of bins [n, F] and targets [n, T] (both
+    included), with an eval set of its own bins and targets per entry of ``eval_rows`` (a set that aliases the
+    training rows: count its margin only, as 0 rows plus ``4 * T * n``)."""
+    foff = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(c) + 1 for c in cuts])]).astype(np.int32))
+    pd = N.query("em_gbdt_partial_doubles", n, T, F, foff.ctypes.data, max_depth)
+    if pd < 0:
+        raise PlanUnsupported(f"GPU GBDT: no histogram plan for depth {max_depth} x {int(foff[-1])} bins x {T} tasks")
+    NN = 2 ** (max_depth + 1) - 1
+    rows = n * (F + 4 * T)  # bins + Y
+    rows += T * n * (4 + 4 + 4 + 2 + 2)  # margin, g, h, node, node2
+    for ne in eval_rows:
+        rows += ne * (F + 4 * T) + 4 * T * ne
+    trees = nround * T * NN * (1 + 2 + 1 + 4 + 4 + 4)
+    return int(rows + 8 * max(pd, 1) + 2 * 8 * T * NN + 8 * 5 * 4096 + trees)
+
+
+def _fit_device(model, d_bins, d_Y, ev_sets, rounds_per_call: int = 500, dp=None):
+    """The rounds, on device tensors: ``d_bins`` uint8 [n, F], ``d_Y`` float32 [n, T] and the eval sets
+    ``(name, bins uint8 [ne, F], Y float32 [ne, T])``.  An eval set may alias the training tensors (they are only
+    read); every set gets a margin buffer of its own here."""
+    dev = d_bins.device
+    n, F = d_bins.shape
+    T = d_Y.shape[1]
+    R, D = model.nround, model.max_depth
+    NN = 2 ** (D + 1) - 1
+    cells = _Cells(model.cuts, dev)
+    margin = torch.empty(T * n, dtype=torch.float32, device=dev)
+    stream = N.stream_handle(dev)
+    N.call("em_gbdt_init_margin", margin.data_ptr(), T * n, float(model.base_margin), stream)
+    ev_names = [name for name, _, _ in ev_sets]
+    ev_keep = []
+    ev_structs = (_Eval * max(1, len(ev_names)))()
+    for i, (name, db, dy) in enumerate(ev_sets):
+        ne = db.shape[0]
+        em = torch.empty(T * ne, dtype=torch.float32, device=dev)
         N.call("em_gbdt_init_margin", em.data_ptr(), em.numel(), float(model.base_margin), stream)
         ev_keep += [db, dy, em]
-        ev_structs[i] = _Eval(db.data_ptr(), dy.data_ptr(), em.data_ptr(), len(ex))
+        ev_structs[i] = _Eval(db.data_ptr(), dy.data_ptr(), em.data_ptr(), ne)
     g = torch.empty(T * n, dtype=torch.float32, device=dev)
     h = torch.empty_like(g)
     node = torch.empty(T * n, dtype=torch.int16, device=dev)
@@ -213,13 +243,11 @@ def _fit_dp_rounds(model, dp, d_bins, d_Y, n, F, cells, T, margin, ev_names, ev_
         model._log_round(rec)
 
 
-def predict_margin(model, X):
-    dev = _dev()
-    tr = model.trees
-    bins = apply_bins(X, model.cuts)
-    n, F = bins.shape
+def _device_margin(model, d_bins: torch.Tensor) -> torch.Tensor:
+    """em_gbdt_predict on device bins uint8 [n, F]: the margins as float32 [T, n] on the device."""
+    dev, tr = d_bins.device, model.trees
+    n, F = d_bins.shape
     T = model.n_tasks
-    NN = 2 ** (tr.max_depth + 1) - 1
     dt = getattr(model, "_device_trees", None)
     if dt is None:
         dt = (torch.from_numpy(tr.status.reshape(-1)).to(dev), torch.from_numpy(tr.feat.astype(np.int16).reshape(-1)).to(dev),
@@ -227,11 +255,24 @@ def predict_margin(model, X):
               torch.from_numpy(tr.leaf.astype(np.float32).reshape(-1)).to(dev))
         model._device_trees = dt
     status, feat, sbin, leaf = dt
-    d_bins = torch.from_numpy(np.ascontiguousarray(bins, dtype=np.uint8)).to(dev)
     margin = torch.full((T * n,), float(model.base_margin), dtype=torch.float32, device=dev)
     N.call("em_gbdt_predict", d_bins.data_ptr(), margin.data_ptr(), T, n, F, tr.max_depth, 0, tr.n_trees,
            status.data_ptr(), feat.data_ptr(), sbin.data_ptr(), leaf.data_ptr(), N.stream_handle(dev))
-    return margin.view(T, n).t().cpu().numpy().astype(np.float64)
+    return margin.view(T, n)
+
+
+def predict_margin(model, X):
+    bins = apply_bins(X, model.cuts)
+    d_bins = torch.from_numpy(np.ascontiguousarray(bins, dtype=np.uint8)).to(_dev())
+    return _device_margin(model, d_bins).t().cpu().numpy().astype(np.float64)
+
+
+def predict_margin_rows(model, d_bins: torch.Tensor) -> torch.Tensor:
+    """Margins of device bins uint8 [n, F] as float32 [n, 64] on the device, task ``t`` in column ``t`` and zeros
+    from column T on: the logit rows ``draw_metrics`` / ``draw_tickets`` read (T <= 64)."""
+    out = torch.zeros(d_bins.shape[0], 64, dtype=torch.float32, device=d_bins.device)
+    out[:, :model.n_tasks] = _device_margin(model, d_bins).t()
+    return out
 
 
 # ----------------------------------------------------------------------------- explanations (csrc/gbdt_shap.hip)

@@ -79,6 +79,19 @@ def fit(X: np.ndarray | torch.Tensor, Y: np.ndarray | torch.Tensor, F: int, t_of
     return feat.cpu().numpy(), value.cpu().numpy(), gain.cpu().numpy(), cover.cpu().numpy()
 
 
+def fit_buffer_bytes(n: int, W: int, F: int, T: int, max_depth: int, k: int) -> int:
+    """Device bytes :func:`fit` allocates for ``T`` trees on ``n`` rows of ``W`` words (the rows X [n, W] and the
+    targets Y [n] included): the shapes above, for a check against the free memory before a large fit."""
+    nodes, half = (1 << (max_depth + 1)) - 1, 1 << max_depth
+    acc_words = N.query("em_rf_acc_words", T, max_depth, k)
+    if acc_words < 0:
+        raise ValueError("unsupported forest shape (trees / depth / candidate count)")
+    row_lists = 2 * T * n * N.query("em_rf_row_bytes", W, F, n)
+    trees = T * nodes * (2 * 4 + 2 + 64 * 4 + 8 + 4)  # seg, feat, value, gain, cover
+    scratch = T * half * k * 2 + acc_words * 4 + T * half * 2 * 4 + (T * half + 1) * 4  # cand, acc, lrc, wl
+    return int(8 * n * (W + 1) + row_lists + trees + scratch)
+
+
 def _predict_args(X, feat, value, max_depth: int, stream_trees: bool, device):
     """What predict and oob_predict share: X, feat and value on the device, the shape check, ``out`` [N, 64] and
     the tree-image scratch.  Returns the leading arguments of either entry point (X, W, N, feat, value, T,

@@ -15,7 +15,9 @@ Differences from the reference, all documented in SURVEY.md §7.5:
   is changed, e.g. ``--objective reg:squarederror``);
 * ``--reference-compat`` reproduces D-f (a second booster trained on the validation
   split) so ``check_predicts`` compares the same two arrays as the reference;
-* errors are reported accurately with a non-zero exit code (D-g).
+* errors are reported accurately with a non-zero exit code (D-g);
+* ``--data-source device`` runs the same steps on draws generated on the GPU: bins, targets, fit, predictions and
+  metrics all read the device masks (:func:`_run_device_pipeline`), and no CSV files are written.
 """
 from __future__ import annotations
 
@@ -92,9 +94,133 @@ def gbdt_dataset(ds: DrawSet, cfg: RunConfig):
     return X, Y, "next-draw"
 
 
+# ---------------------------------------------------------------------------------------------
+# tree models on GPU-generated draws (data.source=device): the masks never leave HBM
+# ---------------------------------------------------------------------------------------------
+def device_tree_guard(cfg: RunConfig, model_device: str) -> None:
+    """What a tree model on ``data.source=device`` cannot run with: data parallelism, no GPU."""
+    from .config import ConfigError
+
+    if cfg.dist.dp > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+        raise ConfigError("data.source=device trains the tree models in a single process (no --dp, no torchrun)")
+    import torch
+
+    if "cpu" in (cfg.device, model_device) or not torch.cuda.is_available():
+        raise ConfigError("data.source=device needs a GPU")
+
+
+def device_draw_count(cfg: RunConfig) -> int:
+    from .data.device_gen import gb_to_draws
+
+    return int(cfg.data.n_draws) if cfg.data.n_draws else gb_to_draws(cfg.data.device_gb)
+
+
+def check_device_memory(need: int, device, what: str) -> None:
+    """Raise before anything is allocated when ``need`` bytes of buffers exceed the free device memory."""
+    import torch
+
+    from .config import ConfigError
+
+    free = int(torch.cuda.mem_get_info(device)[0])
+    if need > free:
+        raise ConfigError(f"{what}: the masks and fit buffers need {int(need)} bytes of device memory, "
+                          f"{free} bytes are free")
+
+
+def device_draw_metrics(masks, logits_of, a: int, b: int, lags: int = 1, loss: str = "bce", chunk: int = 1 << 22) -> dict:
+    """The draw metrics (``csrc/metrics.hip``) of samples ``[a, b)`` of device masks, whose targets are the draws
+    ``s + lags``.  ``logits_of(c0, c1)`` returns the float32 [c1 - c0, 64] device logits of samples ``[c0, c1)``;
+    at most ``chunk`` rows of them exist at a time.  Keys as ``FusedSmallMLP.evaluate``."""
+    from .ops import fused_mlp as FM
+
+    tgt = masks[lags - 1:] if lags > 1 else masks  # the kernel scores sample s against its masks[s + 1]
+    tot = np.zeros(8, dtype=np.float64)
+    for c0 in range(a, b, chunk):
+        c1 = min(b, c0 + chunk)
+        part = FM.draw_metrics(logits_of(c0, c1), tgt, c1 - c0, loss=loss, offset=c0)
+        tot += part.double().sum(0).cpu().numpy()
+    cnt = max(tot[7], 1.0)
+    res = {k: float(tot[i] / cnt) for i, k in enumerate(FM.METRIC_NAMES[:-1])}
+    res["count"] = int(tot[7])
+    return res
+
+
+def _run_device_pipeline(cfg: RunConfig, out, log, t0: float) -> dict:
+    """:func:`run_reference_pipeline` on ``data.source=device``: draws generated on the GPU, the next-draw GBDT
+    fitted from the masks (``GBDT.fit_draw_masks``), watches ``train`` / ``test``, ``val`` from device margins."""
+    from .config import ConfigError
+
+    g = cfg.gbdt
+    if g.target == "reference":
+        raise ConfigError("gbdt.target=reference needs draw dates; data.source=device generates numbers only "
+                          "(use the next-draw target)")
+    if g.objective.startswith("multi:"):
+        raise ConfigError(f"data.source=device trains the 62 binary next-draw boosters; gbdt.objective={g.objective} "
+                          "does not apply")
+    device_tree_guard(cfg, g.device)
+    import torch
+
+    from .data.device_gen import generate_masks
+    from .models import gbdt_hip
+    from .models.gbdt import GBDT, cuts_from_bit_counts
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_draws = device_draw_count(cfg)
+    n = n_draws - 1  # sample s: draw s -> draw s + 1
+    margin = positional_split(n, cfg.data.train_pct)
+    if margin < 1 or n - margin < 1:
+        raise ValueError(f"need draws for a training and a validation split (have {n_draws})")
+    chunk = 1 << 22
+    n_fits = 2 if cfg.reference_compat else 1
+    need = 8 * n_draws + (62 + 4 * 62 + 4 * 64) * min(chunk, max(margin, n - margin))  # masks, one chunk of val rows
+    for k in range(n_fits):  # (upper bound: every column varied; the "train" watch shares the rows of the fit)
+        rows, other = (margin, n - margin) if k == 0 else (n - margin, margin)
+        need = max(need, 8 * n_draws + gbdt_hip.fit_buffer_bytes(
+            rows, 62, 62, cuts_from_bit_counts([1] * 62, 2), g.max_depth, g.nround, eval_rows=(other,)) + 4 * 62 * rows)
+    check_device_memory(need, dev, "gbdt on data.source=device")
+    masks = generate_masks(n_draws, seed=cfg.data.seed, planted=cfg.data.planted, device=dev)
+    log.info(f"generated {n_draws} draws on {dev} ({cfg.data.planted} planted)")
+    mk = dict(nround=g.nround, reg_lambda=g.reg_lambda, min_child_weight=g.min_child_weight,
+              base_score=g.base_score, max_bin=g.max_bin, backend="hip", log=log, log_every=max(1, g.nround // 20))
+    watches = {"train": (0, margin), "test": (margin, n)}
+    booster = GBDT.from_params(cfg.gbdt_params(), **mk).fit_draw_masks(masks, (0, margin), evals=watches)
+    scorer = booster
+    if cfg.reference_compat:  # D-f: the second booster, trained on the validation split
+        scorer = GBDT.from_params(cfg.gbdt_params(), **mk).fit_draw_masks(masks, (margin, n), evals=watches)
+    # Main.checkPredicts on the device: unequal lengths -> false, otherwise the predictions' bit patterns
+    compat = False
+    if margin == n - margin:
+        compat = True
+        for c0 in range(0, margin, chunk):
+            c1 = min(margin, c0 + chunk)
+            pa = booster.predict_margin_draw_masks(masks, (c0, c1))[:, :62]
+            pb = scorer.predict_margin_draw_masks(masks, (margin + c0, margin + c1))[:, :62]
+            if g.objective in ("reg:logistic", "binary:logistic"):
+                pa, pb = (1.0 / (1.0 + torch.exp(-p.double())) for p in (pa, pb))
+            compat = compat and bool(torch.equal(pa.float().contiguous().view(torch.int32),
+                                                 pb.float().contiguous().view(torch.int32)))
+    (out.write if out else print)(str(compat).lower() + ("\n" if out else ""))
+    res = {"pipeline": "reference", "target": "next-draw", "n_draws": n_draws, "n_train": int(margin),
+           "n_val": int(n - margin), "backend": booster.backend_used, "check_predicts": compat,
+           "train_" + booster.eval_metric: booster.history[-1].get("train") if booster.history else None,
+           "val_" + booster.eval_metric: booster.history[-1].get("test") if booster.history else None}
+    res["val"] = device_draw_metrics(masks, lambda c0, c1: booster.predict_margin_draw_masks(masks, (c0, c1)),
+                                     margin, n, loss="bce", chunk=chunk)
+    res["chance"] = M.chance_levels()
+    res["world_size"] = 1
+    if cfg.ckpt.path:
+        booster.save(cfg.ckpt.path)
+        res["checkpoint"] = cfg.ckpt.path
+    res["seconds"] = round(time.time() - t0, 3)
+    res["workdir"] = None  # (no CSV split files: the draws exist on the device only)
+    return res
+
+
 def run_reference_pipeline(cfg: RunConfig, out=None) -> dict:
     log = L.get("Main")
     t0 = time.time()
+    if cfg.data.source == "device":
+        return _run_device_pipeline(cfg, out, log, t0)
     ds = load_draws(cfg)
     log.info(f"loaded {len(ds)} draws from {cfg.data.source} "
              f"({ds.meta.get('planted', 0.0) if cfg.data.source == 'synthetic' else 'n/a'} planted)")

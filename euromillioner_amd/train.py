@@ -566,6 +566,8 @@ def train_rf(cfg: RunConfig) -> dict:
     from .models.losses import draw_metrics_torch
 
     log = L.get("Trainer")
+    if cfg.data.source == "device":
+        return _train_rf_device(cfg, log)
     info = D.init(cfg.dist.backend, cfg.dist.timeout_s, device=cfg.rf.device if cfg.rf.device != "auto" else cfg.device)
     try:
         ds = load_draws(cfg)
@@ -597,6 +599,57 @@ def train_rf(cfg: RunConfig) -> dict:
         return res
     finally:
         D.shutdown(info)
+
+
+def _train_rf_device(cfg: RunConfig, log) -> dict:
+    """``train --model rf --data-source device``: the draws are generated on the GPU and the packed lag-window
+    rows, the fit, the validation logits, the metrics and the out-of-bag score all read device tensors
+    (``ops.tree_inputs``).  Result keys as :func:`train_rf`."""
+    from . import pipeline as P
+    from .data.device_gen import generate_masks
+    from .models.forest import RandomForest, n_candidates
+    from .ops import forest as K
+    from .ops import tree_inputs as TI
+
+    r, lags = cfg.rf, int(cfg.data.lags)
+    P.device_tree_guard(cfg, r.device)
+    if not 1 <= lags <= TI.MAX_LAGS:
+        raise ValueError(f"data.lags={lags}: the forest takes 1..{TI.MAX_LAGS} lags (at most 256 features)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_draws = P.device_draw_count(cfg)
+    n = n_draws - lags
+    margin = positional_split(n, cfg.data.train_pct) if n > 0 else 0
+    if margin < 1:
+        raise ValueError(f"need more draws than lags+1 for a training split (have {n_draws})")
+    rf = RandomForest(r.n_trees, r.max_depth, r.min_samples_leaf, r.feature_subset, r.bootstrap, r.seed, "cuda")
+    F, W, chunk = 62 * lags, TI.rf_words(lags), 1 << 22
+    fit_bytes = K.fit_buffer_bytes(margin, W, F, r.n_trees, r.max_depth, n_candidates(r.feature_subset, F))
+    oob_bytes = (8 * (W + 1) + 64 * 4 + 4) * margin if r.oob else 0  # rows, targets, out, count
+    val_bytes = (8 * (W + 1) + 64 * 4) * min(chunk, n - margin)
+    P.check_device_memory(8 * n_draws + max(fit_bytes, oob_bytes, val_bytes), dev, "rf on data.source=device")
+    masks = generate_masks(n_draws, seed=cfg.data.seed, planted=cfg.data.planted, device=dev)
+    t0 = time.time()
+    rf.fit_draw_masks(masks, lags, rows=(0, margin))
+    secs = time.time() - t0
+    log.info(f"forest: {r.n_trees} trees depth {r.max_depth} on {margin} rows of {n_draws} device draws "
+             f"({rf.backend_used}) in {secs:.3f}s")
+    res = {"model": "rf", "backend": rf.backend_used, "world": 1, "trees": int(len(rf.feat)),
+           "train_samples": margin, "val_samples": n - margin, "seconds": round(secs, 3)}
+    if n > margin:
+        def logits_of(c0, c1):
+            return rf.predict_proba_device(TI.rf_rows(masks, lags, first=c0, count=c1 - c0)[0], out_logit=True)
+
+        res["val"] = P.device_draw_metrics(masks, logits_of, margin, n, lags=lags, loss="bce", chunk=chunk)
+    if r.oob:
+        X, Y, _ = TI.rf_rows(masks, lags, first=0, count=margin)  # the rows of the fit, in its order
+        out, count = K.oob_predict(X, rf.feat, rf.value, rf.max_depth, rf.seed, rf.tree_start)
+        res["oob"] = K.oob_metrics(out, count, Y)
+        imp = rf.feature_importances("gain")
+        res["importances_top"] = [[int(f), float(imp[f])] for f in np.argsort(-imp, kind="stable")[:5]]
+    if cfg.ckpt.path:
+        rf.save(cfg.ckpt.path)
+        res["checkpoint"] = cfg.ckpt.path
+    return res
 
 
 # ---------------------------------------------------------------------------------------------
