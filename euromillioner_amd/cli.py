@@ -8,6 +8,7 @@ runs the whole pipeline (``Main.java:35``).  Here:
     euromillioner train --model mlp    # 62->128->62 MLP on the fused HIP path (DP via torchrun)
     euromillioner train --model mlp-wide | rf | gbdt
     euromillioner train --model rf --data-source device --n-draws 700000   # draws generated on the GPU, never on the host
+    euromillioner train --model counts --ckpt base.cnt     # the transition-count baseline every model is read against
     euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv] [--tickets 5 --temperature 1.0]
     euromillioner backtest --ckpt model.zip --tickets 16   # prize tiers of sampled tickets on the validation split
     euromillioner explain --ckpt model.json [--top 3]      # which of the last draw's numbers push each GBDT pick (TreeSHAP)
@@ -47,6 +48,7 @@ _FLAGS = {
     "--hidden": "mlp.hidden", "--activation": "mlp.activation", "--loss": "mlp.loss", "--lr": "mlp.lr",
     "--batch": "mlp.batch", "--accum": "mlp.accum", "--steps": "mlp.steps", "--epochs": "mlp.epochs", "--dtype": "mlp.dtype",
     "--weight-decay": "mlp.weight_decay", "--eval-every": "mlp.eval_every",
+    "--alpha": "counts.alpha",
     "--dp": "dist.dp", "--backend": "dist.backend", "--bucket-mb": "dist.bucket_mb", "--timeout": "dist.timeout_s",
     "--comm-dtype": "dist.comm_dtype",
     "--fault-at-step": "dist.fault_at_step", "--fault-rank": "dist.fault_rank",
@@ -85,15 +87,15 @@ def build_parser() -> argparse.ArgumentParser:
     sub = ap.add_subparsers(dest="cmd")
     p = sub.add_parser("run", help="reference pipeline (default)")
     _add_common(p)
-    p = sub.add_parser("train", help="train a model (mlp | mlp-wide | rf | gbdt)")
+    p = sub.add_parser("train", help="train a model (mlp | mlp-wide | rf | gbdt | counts)")
     _add_common(p)
-    p.add_argument("--model", default="mlp", choices=["mlp", "mlp-wide", "rf", "gbdt"])
+    p.add_argument("--model", default="mlp", choices=["mlp", "mlp-wide", "rf", "gbdt", "counts"])
     p = sub.add_parser("predict", help="predict the next draw from a checkpoint")
     _add_common(p)
-    p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "rf", "gbdt"])
+    p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "rf", "gbdt", "counts"])
     p = sub.add_parser("backtest", help="play sampled tickets on every validation draw and count prize tiers")
     _add_common(p)
-    p.add_argument("--model", default=None, choices=["mlp", "mlp-wide"])
+    p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "counts"])
     p = sub.add_parser("explain", help="TreeSHAP: the features behind each number a GBDT (.json) or forest (.npz) checkpoint picks")
     _add_common(p)
     p.add_argument("--top", type=int, default=3, help="features listed per picked number")
@@ -137,6 +139,9 @@ def main(argv=None) -> int:
             world, must_spawn = launch.requested_world(cfg.dist.dp)
         except ValueError as e:
             log.error(f"invalid configuration: {e}")
+            return 2
+        if world > 1 and cfg.model == "counts" and a.cmd == "train":
+            log.error("invalid configuration: the count table is fitted in a single process (no --dp, no torchrun)")
             return 2
         if world > 1 and cfg.data.source == "device" and (a.cmd == "run" or cfg.model in ("rf", "gbdt")):
             log.error("invalid configuration: data.source=device trains the tree models in a single process "

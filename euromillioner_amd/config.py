@@ -94,6 +94,11 @@ class RFConfig:
 
 
 @dataclasses.dataclass
+class CountsConfig:
+    alpha: float = 1.0  # additive smoothing of the transition counts (> 0); the lags are data.lags
+
+
+@dataclasses.dataclass
 class MLPConfig:
     model: str = "mlp"  # mlp (62-128-62 fused) | mlp-wide (62-8192-8192-62) | custom
     hidden: tuple = (128,)
@@ -155,11 +160,12 @@ class RunConfig:
     gbdt: GBDTConfig = dataclasses.field(default_factory=GBDTConfig)
     rf: RFConfig = dataclasses.field(default_factory=RFConfig)
     mlp: MLPConfig = dataclasses.field(default_factory=MLPConfig)
+    counts: CountsConfig = dataclasses.field(default_factory=CountsConfig)
     dist: DistConfig = dataclasses.field(default_factory=DistConfig)
     ckpt: CkptConfig = dataclasses.field(default_factory=CkptConfig)
     log: LogConfig = dataclasses.field(default_factory=LogConfig)
     tickets: TicketConfig = dataclasses.field(default_factory=TicketConfig)
-    model: str = "gbdt"  # gbdt | rf | mlp | mlp-wide
+    model: str = "gbdt"  # gbdt | rf | mlp | mlp-wide | counts
     device: str = "auto"
     reference_compat: bool = False  # reproduce D-f (second booster trained on validation) + checkPredicts
 
@@ -251,7 +257,7 @@ def apply_env(cfg: RunConfig, environ=None) -> None:
 
 # enumerated fields: a typo must be a configuration error (exit 2), not a silently ignored value
 CHOICES = {
-    "model": ("gbdt", "rf", "mlp", "mlp-wide"),
+    "model": ("gbdt", "rf", "mlp", "mlp-wide", "counts"),
     "device": ("auto", "cuda", "cpu"),
     "data.source": ("synthetic", "csv", "html", "reference-csv", "device"),
     "gbdt.objective": ("reg:logistic", "binary:logistic", "reg:squarederror", "multi:softprob", "multi:softmax"),
@@ -283,6 +289,10 @@ def validate(cfg: RunConfig) -> RunConfig:
         raise ValueError(f"tickets.n={t.n}: must be in 0..64")
     if not (t.temperature >= 0 and t.temperature != float("inf")):
         raise ValueError(f"tickets.temperature={t.temperature}: must be finite and >= 0 (0 = greedy)")
+    if not cfg.counts.alpha > 0:
+        raise ValueError(f"counts.alpha={cfg.counts.alpha}: must be > 0")
+    if cfg.model == "counts" and not 1 <= cfg.data.lags <= 4:
+        raise ValueError(f"data.lags={cfg.data.lags}: the count table takes 1..4 lags")
     if cfg.data.source == "device" and not cfg.data.n_draws and cfg.data.device_gb <= 0:
         raise ValueError("data.source=device needs data.n_draws or data.device_gb")
     return cfg

@@ -13,6 +13,8 @@ mlp          fused single-launch HIP kernel (62->128->62)     grad all-reduce (C
 mlp-wide     GEMM trainer, 62->8192->8192->62                per-layer async buckets (C1)
 rf           HIP forest engine / numpy oracle                tree-parallel + all-gather (C5)
 gbdt         reference pipeline (XGBoost semantics)          single process
+counts       transition-count table: HIP counts + logits     single process
+             / numpy specification (the baseline)
 ===========  ==============================================  =============================
 
 Data parallelism is one process per device (``torchrun``); every rank reads the same
@@ -653,11 +655,92 @@ def _train_rf_device(cfg: RunConfig, log) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------
+# transition-count baseline
+# ---------------------------------------------------------------------------------------------
+def train_counts(cfg: RunConfig) -> dict:
+    """``train --model counts``: fit the count table on the positional training split, report ``val`` on the rest.
+    On a GPU the counts and the validation logits come from ``csrc/draw_counts.hip``; with ``--device cpu`` (or no
+    GPU) from the numpy specification, which gives the same table."""
+    from .data.draws import mask_bits
+    from .models.count_table import CountTable
+
+    log = L.get("Trainer")
+    if cfg.data.source == "device":
+        return _train_counts_device(cfg, log)
+    lags = int(cfg.data.lags)
+    ds = load_draws(cfg)
+    n = len(ds) - lags
+    margin = positional_split(n, cfg.data.train_pct) if n > 0 else 0
+    if margin < 1:
+        raise ValueError(f"need more draws than lags+1 for a training split (have {len(ds)})")
+    model = CountTable(lags, cfg.counts.alpha, cfg.device)
+    t0 = time.time()
+    if model._use_gpu():
+        from .models.mlp import FusedSmallMLP
+
+        masks = FusedSmallMLP.prepare(ds.numbers)
+        model.fit_draw_masks(masks, 0, margin)
+        val = model.evaluate(masks, n - margin, offset=margin) if n > margin else None
+    else:
+        masks = mask_bits(ds.numbers)
+        model.fit_masks_np(masks, 0, margin)
+        val = model.evaluate_np(masks, margin, n - margin) if n > margin else None
+    secs = time.time() - t0
+    log.info(f"count table: {lags} lag(s), alpha {model.alpha:g} on {margin} samples ({model.backend_used}) in {secs:.3f}s")
+    return _counts_result(cfg, model, margin, n - margin, secs, val)
+
+
+def _counts_result(cfg: RunConfig, model, train_samples: int, val_samples: int, secs: float, val) -> dict:
+    res = {"model": "counts", "backend": model.backend_used, "lags": model.lags, "alpha": model.alpha,
+           "train_samples": int(train_samples), "val_samples": int(val_samples), "seconds": round(secs, 3),
+           "val": val, "checkpoint": None}
+    if cfg.ckpt.path:
+        model.save(cfg.ckpt.path)
+        res["checkpoint"] = cfg.ckpt.path
+    return res
+
+
+def _train_counts_device(cfg: RunConfig, log) -> dict:
+    """``train --model counts --data-source device``: the draws are generated on the GPU and the counts, the
+    validation logits and the metrics all read device tensors.  Result keys as :func:`train_counts`."""
+    from . import pipeline as P
+    from .data.device_gen import generate_masks
+    from .models.count_table import CountTable
+
+    lags = int(cfg.data.lags)
+    P.device_tree_guard(cfg, "auto")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_draws = P.device_draw_count(cfg)
+    n = n_draws - lags
+    margin = positional_split(n, cfg.data.train_pct) if n > 0 else 0
+    if margin < 1:
+        raise ValueError(f"need more draws than lags+1 for a training split (have {n_draws})")
+    chunk = 1 << 22
+    # the masks, one chunk of validation logits, and the counts' and metrics' small buffers
+    P.check_device_memory(8 * n_draws + 64 * 4 * min(chunk, max(n - margin, 1)) + (1 << 22), dev,
+                          "counts on data.source=device")
+    masks = generate_masks(n_draws, seed=cfg.data.seed, planted=cfg.data.planted, device=dev)
+    model = CountTable(lags, cfg.counts.alpha, "cuda")
+    t0 = time.time()
+    model.fit_draw_masks(masks, 0, margin)
+    secs = time.time() - t0
+    log.info(f"count table: {lags} lag(s), alpha {model.alpha:g} on {margin} samples of {n_draws} device draws "
+             f"({model.backend_used}) in {secs:.3f}s")
+    val = None
+    if n > margin:
+        val = P.device_draw_metrics(masks, lambda c0, c1: model.logits(masks, c1 - c0, offset=c0), margin, n,
+                                    lags=lags, loss="softmax", chunk=chunk)
+    return _counts_result(cfg, model, margin, n - margin, secs, val)
+
+
+# ---------------------------------------------------------------------------------------------
 def train(cfg: RunConfig) -> dict:
     if cfg.model in ("mlp", "mlp-wide"):
         return train_mlp(cfg)
     if cfg.model == "rf":
         return train_rf(cfg)
+    if cfg.model == "counts":
+        return train_counts(cfg)
     if cfg.model == "gbdt":
         return run_reference_pipeline(cfg)
     raise ValueError(f"unknown model {cfg.model!r}")
@@ -697,6 +780,18 @@ def predict_next(cfg: RunConfig) -> dict:
             x = np.concatenate([x, featurize_raw(ds)[-1:, :4].astype(np.float64)], axis=1)
         p = np.asarray(g.predict(x))[0]
         kind = "gbdt"
+    elif path.endswith(".cnt"):
+        from .data.draws import mask_bits
+        from .models.count_table import CountTable
+
+        ct = CountTable.load(path, "cpu")
+        if len(ds) < ct.lags:
+            raise ValueError(f"the checkpoint reads {ct.lags} draws, the data gives {len(ds)}")
+        # one row through the numpy specification: the sample whose window is the last `lags` draws
+        z = ct.logits_np(mask_bits(ds.numbers), [len(ds) - ct.lags])[0, :62].astype(np.float64)
+        e = np.exp(z - np.concatenate([np.full(50, z[:50].max()), np.full(12, z[50:].max())]))
+        p = np.concatenate([e[:50] / e[:50].sum(), e[50:] / e[50:].sum()])
+        kind = "counts"
     else:
         from .models import losses as LS
         from .models.mlp import DrawMLP
@@ -724,10 +819,10 @@ def predict_next(cfg: RunConfig) -> dict:
     tc = cfg.tickets
     if tc.n > 0:
         # through the numpy specification (one row): CPU and GPU boxes print the same tickets.  Scores: an
-        # MLP's logits (under bce the sampling weights are the odds), log p for the tree models
+        # MLP's or the count table's logits (under bce the sampling weights are the odds), log p for the tree models
         from . import tickets as TK
 
-        score = z.numpy().astype(np.float64) if kind == "mlp" else TK.log_scores(p)
+        score = z.numpy().astype(np.float64) if kind == "mlp" else z if kind == "counts" else TK.log_scores(p)
         tks, _ = TK.sample_tickets_py(score[None, :62], [len(ds) - 1], tc.n, tc.temperature, tc.seed)
         res["tickets"] = []
         for t in tks[0]:
@@ -844,10 +939,9 @@ def _backtest_numpy(net, ds, lags: int, margin: int, n_samples: int, tc, chunk: 
 
 def backtest(cfg: RunConfig) -> dict:
     """``euromillioner backtest``: play ``tickets.n`` sampled tickets on every draw of the positional validation
-    split and count prize tiers, next to the expectation of uniformly random play.  MLP checkpoints only; on a
+    split and count prize tiers, next to the expectation of uniformly random play.  MLP checkpoints and count tables (``.cnt``, :func:`_backtest_counts`); for an MLP on a
     GPU the logits and the tickets never leave the device (csrc/tickets.hip), on ``--device cpu`` the same
     numbers come from DrawMLP and the numpy specification."""
-    from . import tickets as TK
     from .models.mlp import DrawMLP
     from .ops.tickets import backtest_result
 
@@ -861,6 +955,8 @@ def backtest(cfg: RunConfig) -> dict:
     tc = cfg.tickets
     if tc.n < 1:
         raise ValueError("backtest needs --tickets N with N in 1..64")
+    if path.endswith(".cnt"):
+        return _backtest_counts(cfg, path)
     ck = load_mlp_checkpoint(path)
     sizes, ex = tuple(ck["sizes"]), ck["extra"]
     lags = int(ex.get("lags", sizes[0] // 62))
@@ -891,13 +987,57 @@ def backtest(cfg: RunConfig) -> dict:
         net.load_state_dict(ck["state_dict"])
         r = backtest_result(*_backtest_numpy(net, ds, lags, margin, n_samples, tc), rows, tc.n)
         engine = "numpy"
+    return _backtest_report({"model": "mlp", "checkpoint": path, "engine": engine, "sizes": list(sizes)}, r, rows, tc)
+
+
+def _backtest_counts(cfg: RunConfig, path: str) -> dict:
+    """The count-table half of :func:`backtest` (a ``.cnt`` checkpoint): ``CountTable.backtest`` on a GPU, the numpy
+    specification plus ``sample_tickets_py`` / ``score_tickets_py`` on ``--device cpu``."""
+    from . import tickets as TK
+    from .data.draws import mask_bits
+    from .models.count_table import CountTable
+    from .ops.tickets import backtest_result
+
+    tc = cfg.tickets
+    use_gpu = cfg.device == "cuda" or (cfg.device == "auto" and torch.cuda.is_available())
+    ct = CountTable.load(path, "cuda" if use_gpu else "cpu")
+    ds = load_draws(cfg)
+    n_samples = len(ds) - ct.lags
+    margin = positional_split(n_samples, cfg.data.train_pct)
+    rows = n_samples - margin
+    if rows < 1:
+        raise ValueError("empty validation split")
+    if use_gpu:
+        from .models.mlp import FusedSmallMLP
+
+        masks = FusedSmallMLP.prepare(ds.numbers)
+        r = ct.backtest(masks, rows, tc.n, tc.temperature, tc.seed, offset=margin)
+        engine = "hip"
+    else:
+        masks = mask_bits(ds.numbers)
+        hist, best = np.zeros((6, 3), dtype=np.int64), np.zeros(14, dtype=np.int64)
+        for a in range(margin, n_samples, 1 << 14):  # (row id = sample index, as on the GPU)
+            b = min(a + (1 << 14), n_samples)
+            idx = np.arange(a, b)
+            tks, _ = TK.sample_tickets_py(ct.logits_np(masks, idx), idx, tc.n, tc.temperature, tc.seed)
+            h, bt = TK.score_tickets_py(tks, masks[a + ct.lags:b + ct.lags])
+            hist += h
+            best += bt
+        r = backtest_result(hist, best, rows, tc.n)
+        engine = "numpy"
+    return _backtest_report({"model": "counts", "checkpoint": path, "engine": engine, "lags": ct.lags}, r, rows, tc)
+
+
+def _backtest_report(head: dict, r: dict, rows: int, tc) -> dict:
+    """Print the prize-tier table of a back-test and return its result (``head`` first)."""
+    from . import tickets as TK
+
     tiers, exp_t = TK.tier_counts(r["hist"]), r["uniform"]["tiers"]
     print(f"{rows} draws x {tc.n} tickets (T={tc.temperature:g}, seed {tc.seed}): tickets per prize tier | "
           f"draws by best ticket (uniform play beside each)")
     for k in range(13):
         print(f"{k + 1:>2} {TK.TIER_NAMES[k]:>4} {int(tiers[k]):>12} {exp_t[k]:>14.3f} | "
               f"{int(r['best'][k]):>12} {r['uniform']['best'][k]:>14.3f}")
-    return {"model": "mlp", "checkpoint": path, "engine": engine, "sizes": list(sizes), "rows": rows,
-            "tickets": r["tickets"], "n_tickets": tc.n, "temperature": tc.temperature, "seed": tc.seed,
+    return {**head, "rows": rows, "tickets": r["tickets"], "n_tickets": tc.n, "temperature": tc.temperature, "seed": tc.seed,
             "hist": r["hist"].tolist(), "best": r["best"].tolist(), "tiers": tiers.tolist(),
             "uniform": {k: np.asarray(v).tolist() for k, v in r["uniform"].items()}}
