@@ -1381,8 +1381,14 @@ static int gemm_impl(const void* A, int64_t lda, int a_kc, const void* B, int64_
     (void)hipFuncSetAttribute((const void*)gemm_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     attr = true;
   }
+  // the 256-tile and skinny-K epilogues store bf16 C and C^T rows, and load the act' mask, as 16-byte
+  // vectors: a bf16 output (mask, C^T) that is not 16-byte aligned with an 8-element leading dimension
+  // takes the any-layout kernel's scalar epilogue (which has no C^T / colpart / bits: EM_ERR_ARG below)
+  const bool vec_ok = !c_bf16 || ((((uintptr_t)C & 15) == 0 && (ldc & 7) == 0) &&
+                                  (!mask || (((uintptr_t)mask & 15) == 0 && (ldm & 7) == 0)) &&
+                                  (!ct || (((uintptr_t)ct & 15) == 0 && (ldct & 7) == 0)));
   const bool big = splits == 1 && (M % G_BM) == 0 && (N % G_BN) == 0 && (K % G_BK) == 0 && K > 0 &&
-                   (((uintptr_t)A | (uintptr_t)B) & 15) == 0 &&
+                   (((uintptr_t)A | (uintptr_t)B) & 15) == 0 && vec_ok &&
                    (c_bf16 || (act == ACT_NONE && !mask)) &&  // fp32 + act / act' epilogues: any-layout kernel
                    g_layout_ok(a_kc, b_kc, c_bf16, act, mask, dact, ct, bits, lda, ldb, K);
   // skinny K (64 / 128) with a bf16 output: the store-stream kernel (see gemm_k64_kernel)
