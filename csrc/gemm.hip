@@ -20,7 +20,9 @@
 // chunk ^ k&15) and read as MFMA fragments with ds_read_b64_tr_b16.  Block ids are
 // remapped so neighbouring tiles share an XCD's L2 (§5.5 T1, bijective form).
 #include <cstdlib>
+#include <type_traits>
 
+#include "act.h"
 #include "common.h"
 
 namespace {
@@ -28,8 +30,6 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 64, NT = 256;
 constexpr int TILE_BYTES = BM * BK * 2;  // 16 KB per operand per stage
 constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES;
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2, ACT_TANH = 3 };
 
 EM_DEVICE uint32_t kc_off(int row, int chunk) { return row * 128 + (((chunk ^ (row & 7))) << 4); }     // [128][64]
 EM_DEVICE uint32_t mc_off(int krow, int chunk) { return krow * 256 + (((chunk ^ (krow & 15))) << 4); }  // [64][128]
@@ -96,15 +96,6 @@ EM_DEVICE bf16x8 frag(const char* lds, int rc, int s, int lane) {
   const uint32_t o0 = mc_off(kr, col >> 3) + (col & 7) * 2;
   const uint32_t o1 = mc_off(kr + 4, col >> 3) + (col & 7) * 2;
   return cat_tr(lds_tr16(lds, o0), lds_tr16(lds, o1));
-}
-
-EM_DEVICE float apply_act(float x, int act) {
-  switch (act) {
-    case ACT_RELU: return fmaxf(x, 0.f);
-    case ACT_SIGMOID: return 1.f / (1.f + __expf(-x));
-    case ACT_TANH: return tanhf(x);
-    default: return x;
-  }
 }
 
 template <int A_KC, int B_KC>
@@ -186,11 +177,8 @@ gemm_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __restrict_
         const int row = m0 + wm * 64 + 32 * i + (v & 3) + 8 * (v >> 2) + 4 * h;
         if (row >= M) continue;
         float x = alpha * acc[i][j][v] + bv;
-        x = apply_act(x, act);
-        if (mask) {
-          const float y = (float)mask[(int64_t)row * ldm + col];
-          x *= dact == ACT_RELU ? (y > 0.f ? 1.f : 0.f) : dact == ACT_SIGMOID ? y * (1.f - y) : 1.f - y * y;
-        }
+        x = act_fn(x, act);
+        if (mask) x *= act_dfn((float)mask[(int64_t)row * ldm + col], dact);
         if (c_bf16) {
           reinterpret_cast<__bf16*>(C)[(int64_t)row * ldc + col] = (__bf16)x;
         } else {
@@ -308,20 +296,6 @@ EM_DEVICE bf16x8 g_frag(const char* l, int row0, int ks, int lane) {
   return cat_tr(lds_tr16(l, o), lds_tr16(l, o + 256));  // k-rows + 0..3, + 4..7
 }
 
-template <int FN>
-EM_DEVICE float g_fn(float v) {
-  if (FN == ACT_RELU) return fmaxf(v, 0.f);
-  if (FN == ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-  if (FN == ACT_TANH) return tanhf(v);
-  return v;
-}
-template <int FN>
-EM_DEVICE float g_dfn(float y) {  // activation derivative from the saved output y
-  if (FN == ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (FN == ACT_SIGMOID) return y * (1.f - y);
-  return 1.f - y * y;
-}
-
 // ReLU activity bits, uint32 [M / 32][N]: bit (m & 31) of word (m >> 5) * N + n is output[m][n] > 0.
 // A forward epilogue with relu writes them next to its bf16 output; the relu dgrad of the layer above
 // reads one dword per lane and 32-row block instead of staging the 32 x 64 bf16 activation block.
@@ -413,16 +387,14 @@ EM_DEVICE f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
 // OUT_BF16: 1 -> bf16 C (optionally + transposed C^T when HAS_CT), 0 -> fp32 C (+ beta * C_old)
 // FN: activation (DACT = 0, applied to alpha*acc + bias) or activation' (DACT = 1, multiplies
 // alpha*acc by act'(mask[m][n]))
-// G_CROW = 1: bf16 C rows leave through a row image, 8 lanes per 128-B row (see gemm_k64_kernel)
-#ifndef G_CROW
-#define G_CROW 1
-#endif
+// bf16 C rows leave through a row image, 8 lanes per 128-B row (see gemm_k64_kernel; the direct 16-B-per-line
+// stores measured slower: profiles/r3/wide_epilogues.md)
 // g_epilogue for the 16x16 accumulator layout: per 32-row block i the lane's values land in the
 // same transposed per-wave LDS tile T[64 cols][32 rows] (4 consecutive rows = one 8-B write), so
 // everything after the tile is shared with the 32x32 form.
-// acc[mb][nb0 + nb] (nb = 0..3) is the wave's 128 x 64 block at rows rowbase.., cols colw..
-template <int OUT_BF16, int FN, int DACT, int HAS_CT, int NBT>
-EM_DEVICE void g_epilogue16(f32x4 (&acc)[8][NBT], int nb0, char* smem, int wave, int lane, int rowbase, int colw,
+// acc[mb][nb] (nb = 0..3) is the wave's 128 x 64 block at rows rowbase.., cols colw..
+template <int OUT_BF16, int FN, int DACT, int HAS_CT>
+EM_DEVICE void g_epilogue16(f32x4 (&acc)[8][4], char* smem, int wave, int lane, int rowbase, int colw,
                             void* __restrict__ C, int64_t ldc, __bf16* __restrict__ CT, int64_t ldct,
                             const float* __restrict__ bias, const __bf16* __restrict__ mask, int64_t ldm, float alpha,
                             float beta, float* __restrict__ colpart, int N, uint32_t* __restrict__ bits) {
@@ -467,16 +439,17 @@ EM_DEVICE void g_epilogue16(f32x4 (&acc)[8][NBT], int nb0, char* smem, int wave,
       const float bv = (!DACT && bias) ? bias[colw + lc] : 0.f;
 #pragma unroll
       for (int tm = 0; tm < 2; ++tm) {
-        const f32x4& a = acc[2 * i + tm][nb0 + nb];
+        const f32x4& a = acc[2 * i + tm][nb];
         float x[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int lr = 16 * tm + r4 + e;
           float v = alpha * a[e];
           if (DACT) {
-            v = bits ? bit_mul(bw[nb], lr, v) : v * g_dfn<FN>((float)*reinterpret_cast<const __bf16*>(yb + lr * YS + lc * 2));
+            v = bits ? bit_mul(bw[nb], lr, v)
+                     : v * act_dfn((float)*reinterpret_cast<const __bf16*>(yb + lr * YS + lc * 2), FN);
           } else {
-            v = g_fn<FN>(v + bv);
+            v = act_fn(v + bv, FN);
             if (WBITS) bw[nb] |= (v > 0.f ? 1u : 0u) << (16 * tm + e);
           }
           x[e] = v;
@@ -509,19 +482,15 @@ EM_DEVICE void g_epilogue16(f32x4 (&acc)[8][NBT], int nb0, char* smem, int wave,
         const s16x4 lo = lds_tr16(tb, (uint32_t)((cb + q4) * TS + (r0 + 4 * p4) * 2));
         const s16x4 hi = lds_tr16(tb, (uint32_t)((cb + 4 + q4) * TS + (r0 + 4 * p4) * 2));
         const bf16x8 v8 = cat_tr(lo, hi);
-        if (G_CROW)  // row image [32 rows][128 B] in the (consumed) Y block, chunk c of a row at c ^ (row & 7)
-          *reinterpret_cast<bf16x8*>(yb + row * 128 + (((cb >> 3) ^ (row & 7)) << 4)) = v8;
-        else
-          *reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(C) + (int64_t)(rowb + row) * ldc + colw + cb) = v8;
+        // row image [32 rows][128 B] in the (consumed) Y block, chunk c of a row at c ^ (row & 7)
+        *reinterpret_cast<bf16x8*>(yb + row * 128 + (((cb >> 3) ^ (row & 7)) << 4)) = v8;
       }
-      if (G_CROW) {  // 8 lanes per 128-B row segment: each store covers 8 whole lines (as gemm_k64_kernel)
-        wave_lds_sync();
+      wave_lds_sync();  // 8 lanes per 128-B row segment: each store covers 8 whole lines (as gemm_k64_kernel)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int q = lane + 64 * k, row = q >> 3, ch = q & 7;
-          *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(C) + (int64_t)(rowb + row) * ldc + colw + ch * 8) =
-              *reinterpret_cast<const u32x4*>(yb + row * 128 + ((ch ^ (row & 7)) << 4));
-        }
+      for (int k = 0; k < 4; ++k) {
+        const int q = lane + 64 * k, row = q >> 3, ch = q & 7;
+        *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(C) + (int64_t)(rowb + row) * ldc + colw + ch * 8) =
+            *reinterpret_cast<const u32x4*>(yb + row * 128 + ((ch ^ (row & 7)) << 4));
       }
       if (HAS_CT) {
 #pragma unroll
@@ -564,8 +533,17 @@ __device__ uint64_t g_gstamps[G_STAMP_BLOCKS * 8 * 8];
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");   \
     __builtin_amdgcn_sched_barrier(0);                                            \
   } while (0)
+// close segment k: its time since the previous stamp goes to st_acc[k]
+#define G_SEG(k)            \
+  do {                      \
+    uint64_t t_;            \
+    G_MARK(t_);             \
+    st_acc[k] += t_ - st_a; \
+    st_a = t_;              \
+  } while (0)
 #else
 #define G_MARK(t) (void)0
+#define G_SEG(k) (void)0
 #endif
 
 // The fragment reads are spread evenly over the four load segments of a K-tile (at most 8
@@ -584,11 +562,9 @@ gemm256_pp16_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __r
                     const float* __restrict__ bias, const __bf16* __restrict__ mask, int64_t ldm, float alpha,
                     float beta, float* __restrict__ colpart, uint32_t* __restrict__ bits) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+#if G_STAMPS
   uint64_t st_acc[8] = {}, st_t0 = 0, st_a = 0, st_b = 0;
-  (void)st_acc;
-  (void)st_t0;
-  (void)st_a;
-  (void)st_b;
+#endif
   G_MARK(st_t0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
@@ -654,36 +630,16 @@ gemm256_pp16_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __r
       }
     }
     const bool staged = pp_stage_slot<AMN, BMN>(pa, pb, smem, slot, ktiles, wi);
-    if (G_STAMPS) {
-      uint64_t t;
-      G_MARK(t);
-      st_acc[0] += t - st_a;
-      st_a = t;
-    }
+    G_SEG(0);
     if (!staged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    if (G_STAMPS) {
-      uint64_t t;
-      G_MARK(t);
-      st_acc[1] += t - st_a;
-      st_a = t;
-    }
+    G_SEG(1);
     __builtin_amdgcn_s_barrier();
-    if (G_STAMPS) {
-      uint64_t t;
-      G_MARK(t);
-      st_acc[2] += t - st_a;
-      st_a = t;
-    }
+    G_SEG(2);
   };
   auto mfma_seg = [&](int q) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (G_STAMPS) {
-      uint64_t t;
-      G_MARK(t);
-      st_acc[3] += t - st_a;
-      st_a = t;
-    }
+    G_SEG(3);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -695,24 +651,14 @@ gemm256_pp16_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __r
           c = mfma16(fa[q & 1][ii][ks], fb[jj][ks], c);
         }
     __builtin_amdgcn_s_setprio(0);
-    if (G_STAMPS) {
-      uint64_t t;
-      G_MARK(t);
-      st_acc[4] += t - st_a;
-      st_a = t;
-    }
+    G_SEG(4);
     __builtin_amdgcn_s_barrier();
-    if (G_STAMPS) {
-      uint64_t t;
-      G_MARK(t);
-      st_acc[5] += t - st_a;
-      st_a = t;
-    }
+    G_SEG(5);
   };
-  if (G_STAMPS) {
-    G_MARK(st_a);
-    st_acc[6] = st_a - st_t0;
-  }
+#if G_STAMPS
+  G_MARK(st_a);
+  st_acc[6] = st_a - st_t0;
+#endif
 
   if (!g1) {
     load_seg(0, -1);
@@ -737,9 +683,11 @@ gemm256_pp16_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __r
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (G_STAMPS) G_MARK(st_b);
-  g_epilogue16<OUT_BF16, FN, DACT, HAS_CT, 4>(acc, 0, smem, wave, lane, m0 + wm * 128, n0 + wn * 64, C, ldc, CT,
-                                              ldct, bias, mask, ldm, alpha, beta, colpart, N, bits);
+#if G_STAMPS
+  G_MARK(st_b);
+#endif
+  g_epilogue16<OUT_BF16, FN, DACT, HAS_CT>(acc, smem, wave, lane, m0 + wm * 128, n0 + wn * 64, C, ldc, CT, ldct, bias,
+                                           mask, ldm, alpha, beta, colpart, N, bits);
 #if G_STAMPS
   {
     uint64_t t;
@@ -752,83 +700,96 @@ gemm256_pp16_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __r
 #endif
 }
 
-template <int OUT_BF16, int FN, int DACT, int HAS_CT, int AMN = 0, int BMN = 0>
-int g_launch(dim3 grid, hipStream_t st, const __bf16* A, int64_t lda, const __bf16* B, int64_t ldb, void* C,
-             int64_t ldc, __bf16* CT, int64_t ldct, int M, int N, int K, const float* bias, const __bf16* mask,
-             int64_t ldm, float alpha, float beta, float* colpart, uint32_t* bits) {
+// ============================================================================================
+// Host side.  One call = one GemmArgs (the entry points' arguments in their order, pointers typed).  It
+// stays on the host: every kernel is launched with its own scalar parameter list.
+struct GemmArgs {
+  const __bf16* A;
+  int64_t lda;
+  int a_kc;
+  const __bf16* B;
+  int64_t ldb;
+  int b_kc;
+  void* C;
+  int64_t ldc;
+  int c_bf16;
+  int M, N, K;
+  const float* bias;
+  int act;
+  const __bf16* mask;
+  int64_t ldm;
+  int dact;
+  float alpha, beta;
+  __bf16* ct;
+  int64_t ldct;
+  int splits, kstep;
+  int64_t c_split;
+  float* colpart;
+  uint32_t* bits;
+};
+
+// raise KERN's dynamic-LDS limit to BYTES: once per process and kernel, on the kernel's first launch
+template <auto KERN, int BYTES>
+void lds_limit_once() {
+  static const bool done =
+      ((void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES), true);
+  (void)done;
+}
+
+// runtime epilogue choice -> compile-time constants: f(IC<FN>, IC<DACT>, IC<HAS_CT>) with FN the activation
+// (DACT = 0) or the activation whose derivative is applied (DACT = 1).  The 256-tile and the skinny-K
+// dispatch both go through here; which combinations exist as kernels is theirs to say (if constexpr).
+template <int V>
+using IC = std::integral_constant<int, V>;
+template <class F>
+int with_epilogue(int fn, bool is_dact, bool has_ct, F f) {
+  auto flags = [&](auto FN) {
+    if (is_dact) return has_ct ? f(FN, IC<1>{}, IC<1>{}) : f(FN, IC<1>{}, IC<0>{});
+    return has_ct ? f(FN, IC<0>{}, IC<1>{}) : f(FN, IC<0>{}, IC<0>{});
+  };
+  switch (fn) {
+    case ACT_NONE: return flags(IC<ACT_NONE>{});
+    case ACT_RELU: return flags(IC<ACT_RELU>{});
+    case ACT_SIGMOID: return flags(IC<ACT_SIGMOID>{});
+    case ACT_TANH: return flags(IC<ACT_TANH>{});
+    default: return EM_ERR_ARG;
+  }
+}
+
+template <int OUT_BF16, int FN, int DACT, int HAS_CT, int AMN, int BMN>
+int g_launch(const GemmArgs& g, hipStream_t st) {
   // (the 32x32x16 ping-pong kernel, the non-ping-pong 256 kernel and the unbalanced fragment-read
   // schedule were measured slower and removed in round 5; docs/DESIGN.md §2 and §6 keep their numbers)
-  static bool attr = false;
-  auto kern = gemm256_pp16_kernel<OUT_BF16, FN, DACT, HAS_CT, AMN, BMN>;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS);
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(G_NT), G_LDS, st, A, lda, B, ldb, C, ldc, CT, ldct, M, N, K, bias, mask, ldm,
-                     alpha, beta, colpart, bits);
+  constexpr auto kern = gemm256_pp16_kernel<OUT_BF16, FN, DACT, HAS_CT, AMN, BMN>;
+  lds_limit_once<kern, G_LDS>();
+  hipLaunchKernelGGL(kern, dim3((g.M / G_BM) * (g.N / G_BN)), dim3(G_NT), G_LDS, st, g.A, g.lda, g.B, g.ldb, g.C,
+                     g.ldc, g.ct, g.ldct, g.M, g.N, g.K, g.bias, g.mask, g.ldm, g.alpha, g.beta, g.colpart, g.bits);
   return 0;
 }
 
-// runtime (layout, out, act/dact, ct) -> one of 20 instantiations.  Layouts besides NT (a_kc = b_kc = 1):
+// runtime (layout, out, act / dact, ct) -> one of 20 instantiations.  Layouts besides NT (a_kc = b_kc = 1):
 // wgrad dW = dZ^T X from the natural [batch][features] tensors (both operands MN: fp32 out, no
 // activation) and dgrad (dZ W) * act' from the natural weight (B MN: bf16 out, act' or none, no C^T).
-// Whether a layout is taken is decided by g_layout_ok.
-int g_dispatch(dim3 grid, hipStream_t st, int a_kc, int b_kc, const __bf16* A, int64_t lda, const __bf16* B,
-               int64_t ldb, void* C, int64_t ldc, int c_bf16, __bf16* CT, int64_t ldct, int M, int N, int K,
-               const float* bias, int act, const __bf16* mask, int64_t ldm, int dact, float alpha, float beta,
-               float* colpart, uint32_t* bits) {
-#define EM_GL(OB, FN, DA, CTV, AM, BM)                                                                              \
-  return g_launch<OB, FN, DA, CTV, AM, BM>(grid, st, A, lda, B, ldb, C, ldc, CT, ldct, M, N, K, bias, mask, ldm, alpha, \
-                                           beta, colpart, bits)
-#define EM_G(OB, FN, DA, CTV) EM_GL(OB, FN, DA, CTV, 0, 0)
-  if (!a_kc && !b_kc) {
-    if (c_bf16 || act != ACT_NONE || mask || dact || CT || bits) return EM_ERR_ARG;
-    EM_GL(0, ACT_NONE, 0, 0, 1, 1);
-  }
-  if (!b_kc) {
-    if (!a_kc || !c_bf16 || act != ACT_NONE || CT) return EM_ERR_ARG;
-    switch (dact) {
-      case 0: EM_GL(1, ACT_NONE, 0, 0, 0, 1);
-      case ACT_RELU: EM_GL(1, ACT_RELU, 1, 0, 0, 1);
-      case ACT_SIGMOID: EM_GL(1, ACT_SIGMOID, 1, 0, 0, 1);
-      case ACT_TANH: EM_GL(1, ACT_TANH, 1, 0, 0, 1);
-      default: return EM_ERR_ARG;
+// gemm_route sends only these here; the EM_ERR_ARG arms close the template cross product, no call reaches them.
+int g_dispatch(const GemmArgs& g, hipStream_t st) {
+  return with_epilogue(g.dact ? g.dact : g.act, g.dact != 0, g.ct != nullptr, [&](auto fn, auto da, auto ct) {
+    constexpr int FN = decltype(fn)::value, DA = decltype(da)::value, CT = decltype(ct)::value;
+    if constexpr (DA && FN == ACT_NONE) {
+      return EM_ERR_ARG;
+    } else {
+      if (!g.c_bf16) {  // fp32 output: plain, NT or both operands MN
+        if constexpr (FN == ACT_NONE && !CT)
+          return g.a_kc ? g_launch<0, ACT_NONE, 0, 0, 0, 0>(g, st) : g_launch<0, ACT_NONE, 0, 0, 1, 1>(g, st);
+        else
+          return EM_ERR_ARG;
+      }
+      if (!g.b_kc) {
+        if constexpr (!CT && (DA || FN == ACT_NONE)) return g_launch<1, FN, DA, 0, 0, 1>(g, st);
+        else return EM_ERR_ARG;
+      }
+      return g_launch<1, FN, DA, CT, 0, 0>(g, st);
     }
-  }
-  if (!a_kc) return EM_ERR_ARG;
-  if (!c_bf16) {
-    if (act != ACT_NONE || mask || dact || CT || bits) return EM_ERR_ARG;
-    EM_G(0, ACT_NONE, 0, 0);
-  }
-  const bool ct = CT != nullptr;
-  if (mask || dact) {
-    if (act != ACT_NONE) return EM_ERR_ARG;
-    switch (dact) {
-      case ACT_RELU: if (ct) EM_G(1, ACT_RELU, 1, 1); else EM_G(1, ACT_RELU, 1, 0);
-      case ACT_SIGMOID: if (ct) EM_G(1, ACT_SIGMOID, 1, 1); else EM_G(1, ACT_SIGMOID, 1, 0);
-      case ACT_TANH: if (ct) EM_G(1, ACT_TANH, 1, 1); else EM_G(1, ACT_TANH, 1, 0);
-      default: return EM_ERR_ARG;
-    }
-  }
-  switch (act) {
-    case ACT_NONE: if (ct) EM_G(1, ACT_NONE, 0, 1); else EM_G(1, ACT_NONE, 0, 0);
-    case ACT_RELU: if (ct) EM_G(1, ACT_RELU, 0, 1); else EM_G(1, ACT_RELU, 0, 0);
-    case ACT_SIGMOID: if (ct) EM_G(1, ACT_SIGMOID, 0, 1); else EM_G(1, ACT_SIGMOID, 0, 0);
-    case ACT_TANH: if (ct) EM_G(1, ACT_TANH, 0, 1); else EM_G(1, ACT_TANH, 0, 0);
-    default: return EM_ERR_ARG;
-  }
-#undef EM_G
-#undef EM_GL
-}
-
-// The 256-tile kernel's layouts (see g_dispatch); MN operands need 32-bit buffer offsets over all of K
-bool g_layout_ok(int a_kc, int b_kc, int c_bf16, int act, const void* mask, int dact, const void* ct,
-                 const void* bits, int64_t lda, int64_t ldb, int K) {
-  if (a_kc && b_kc) return true;
-  if ((!a_kc && (int64_t)K * lda * 2 >= (1ll << 31)) || (!b_kc && (int64_t)K * ldb * 2 >= (1ll << 31))) return false;
-  if (!a_kc && !b_kc) return !c_bf16 && act == ACT_NONE && !mask && !dact && !ct && !bits;
-  if (!b_kc) return c_bf16 && act == ACT_NONE && !ct;
-  return false;
+  });
 }
 
 // bf16 transpose: dst[c][r] = src[r][c]; 64x64 tiles through LDS, 16-B global accesses
@@ -988,9 +949,9 @@ gemm_k64_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __restr
         for (int e = 0; e < 4; ++e) {
           float v = alpha * acc[i][j][4 * g + e];
           if (DACT) {
-            v = bits ? bit_mul(bw[i][j], 8 * g + 4 * h + e, v) : v * g_dfn<FN>(y[e]);
+            v = bits ? bit_mul(bw[i][j], 8 * g + 4 * h + e, v) : v * act_dfn(y[e], FN);
           } else {
-            v = g_fn<FN>(v + bv);
+            v = act_fn(v + bv, FN);
             if (WBITS) bw[i][j] |= (v > 0.f ? 1u : 0u) << (8 * g + e);
           }
           x[e] = v;
@@ -1056,45 +1017,23 @@ gemm_k64_kernel(const __bf16* __restrict__ A, int64_t lda, const __bf16* __restr
 }
 
 template <int FN, int DACT, int HAS_CT>
-int k64_launch(hipStream_t st, const __bf16* A, int64_t lda, const __bf16* B, int64_t ldb, __bf16* C, int64_t ldc,
-               __bf16* CT, int64_t ldct, int M, int N, int K, const float* bias, const __bf16* mask, int64_t ldm,
-               float alpha, float* colpart, uint32_t* bits) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_k64_kernel<FN, DACT, HAS_CT>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, K64_LDS);
-    attr = true;
-  }
-  const int lds = (DACT && !bits) ? K64_LDS : K64_LDS_SLIM;  // (the staged act' mask needs its 32 KB)
-  hipLaunchKernelGGL((gemm_k64_kernel<FN, DACT, HAS_CT>), dim3((M / K64_BM) * (N / K64_BN)), dim3(K64_NT), lds, st,
-                     A, lda, B, ldb, C, ldc, CT, ldct, M, N, K, bias, mask, ldm, alpha, colpart, bits);
+int k64_launch(const GemmArgs& g, hipStream_t st) {
+  constexpr auto kern = gemm_k64_kernel<FN, DACT, HAS_CT>;
+  lds_limit_once<kern, K64_LDS>();
+  const int lds = (DACT && !g.bits) ? K64_LDS : K64_LDS_SLIM;  // (the staged act' mask needs its 32 KB)
+  hipLaunchKernelGGL(kern, dim3((g.M / K64_BM) * (g.N / K64_BN)), dim3(K64_NT), lds, st, g.A, g.lda, g.B, g.ldb,
+                     (__bf16*)g.C, g.ldc, g.ct, g.ldct, g.M, g.N, g.K, g.bias, g.mask, g.ldm, g.alpha, g.colpart,
+                     g.bits);
   return 0;
 }
 
-// runtime (act / dact, ct) -> instantiation; bf16 output only
-int k64_dispatch(hipStream_t st, const __bf16* A, int64_t lda, const __bf16* B, int64_t ldb, __bf16* C, int64_t ldc,
-                 __bf16* CT, int64_t ldct, int M, int N, int K, const float* bias, int act, const __bf16* mask,
-                 int64_t ldm, int dact, float alpha, float* colpart, uint32_t* bits) {
-#define EM_K(FN, DA, CTV) \
-  return k64_launch<FN, DA, CTV>(st, A, lda, B, ldb, C, ldc, CT, ldct, M, N, K, bias, mask, ldm, alpha, colpart, bits)
-  const bool ct = CT != nullptr;
-  if (mask || dact) {
-    if (act != ACT_NONE) return EM_ERR_ARG;
-    switch (dact) {
-      case ACT_RELU: if (ct) EM_K(ACT_RELU, 1, 1); else EM_K(ACT_RELU, 1, 0);
-      case ACT_SIGMOID: if (ct) EM_K(ACT_SIGMOID, 1, 1); else EM_K(ACT_SIGMOID, 1, 0);
-      case ACT_TANH: if (ct) EM_K(ACT_TANH, 1, 1); else EM_K(ACT_TANH, 1, 0);
-      default: return EM_ERR_ARG;
-    }
-  }
-  switch (act) {
-    case ACT_NONE: if (ct) EM_K(ACT_NONE, 0, 1); else EM_K(ACT_NONE, 0, 0);
-    case ACT_RELU: if (ct) EM_K(ACT_RELU, 0, 1); else EM_K(ACT_RELU, 0, 0);
-    case ACT_SIGMOID: if (ct) EM_K(ACT_SIGMOID, 0, 1); else EM_K(ACT_SIGMOID, 0, 0);
-    case ACT_TANH: if (ct) EM_K(ACT_TANH, 0, 1); else EM_K(ACT_TANH, 0, 0);
-    default: return EM_ERR_ARG;
-  }
-#undef EM_K
+// runtime (act / dact, ct) -> one of 14 instantiations; bf16 output only
+int k64_dispatch(const GemmArgs& g, hipStream_t st) {
+  return with_epilogue(g.dact ? g.dact : g.act, g.dact != 0, g.ct != nullptr, [&](auto fn, auto da, auto ct) {
+    constexpr int FN = decltype(fn)::value, DA = decltype(da)::value, CT = decltype(ct)::value;
+    if constexpr (DA && FN == ACT_NONE) return EM_ERR_ARG;  // (closes the cross product: never called)
+    else return k64_launch<FN, DA, CT>(g, st);
+  });
 }
 
 // column sums of a bf16 [M][N] matrix (bias gradients), deterministic two-pass:
@@ -1133,7 +1072,7 @@ __global__ void __launch_bounds__(256) colsum_partial_kernel(const __bf16* __res
 // chunk groups per 1024-thread block; group g sums chunks g, g + 16, ... with 8 loads in flight, then
 // the 16 group sums are added in group order (bit-reproducible, and one round of loads deep instead
 // of a serial walk over the chunks).  Used for the colsum partials and for the GEMM epilogue's fused
-// bias-gradient partials (em_gemm_bf16_cs).
+// bias-gradient partials (em_gemm_bf16's colpart).
 constexpr int CR_COLS = 64, CR_G = 16;
 __global__ void __launch_bounds__(CR_COLS * CR_G) colsum_final_kernel(const float* __restrict__ part, int chunks, int N,
                                                                       float* __restrict__ out, int accumulate,
@@ -1308,41 +1247,92 @@ wgrad_skinny_reduce_kernel(const float* __restrict__ part, int S, int J, int W, 
 
 }  // namespace
 
-static int gemm_impl(const void* A, int64_t lda, int a_kc, const void* B, int64_t ldb, int b_kc, void* C,
-                     int64_t ldc, int c_bf16, int M, int N, int K, const float* bias, int act, const void* mask,
-                     int64_t ldm, int dact, float alpha, float beta, void* ct, int64_t ldct, int splits, int kstep,
-                     int64_t c_split, hipStream_t stream, float* colpart = nullptr, uint32_t* bits = nullptr);
+// Which kernel family serves a (validated) call: the one place where that is decided.
+enum GemmPath { GEMM_REFUSE, GEMM_ANY, GEMM_256, GEMM_K64 };
 
+static GemmPath gemm_route(const GemmArgs& g) {
+  const bool nt = g.a_kc && g.b_kc;
+  // The 256-tile and skinny-K epilogues store bf16 C and C^T rows, and load the act' mask, as 16-byte
+  // vectors: a bf16 output (mask, C^T) that is not 16-byte aligned with an 8-element leading dimension
+  // takes the any-layout kernel's scalar epilogue.
+  const bool vec_ok = !g.c_bf16 || ((((uintptr_t)g.C & 15) == 0 && (g.ldc & 7) == 0) &&
+                                    (!g.mask || (((uintptr_t)g.mask & 15) == 0 && (g.ldm & 7) == 0)) &&
+                                    (!g.ct || (((uintptr_t)g.ct & 15) == 0 && (g.ldct & 7) == 0)));
+  // The 256-tile kernel's layouts besides NT (see g_dispatch): both operands MN for a plain fp32 output,
+  // B MN for a bf16 output without activation or C^T; MN operands need 32-bit buffer offsets over all of K.
+  bool layout_ok = nt;
+  if (!nt && !(!g.a_kc && (int64_t)g.K * g.lda * 2 >= (1ll << 31)) &&
+      !(!g.b_kc && (int64_t)g.K * g.ldb * 2 >= (1ll << 31))) {
+    if (!g.a_kc && !g.b_kc) layout_ok = !g.c_bf16 && g.act == ACT_NONE && !g.mask && !g.dact && !g.ct && !g.bits;
+    else if (!g.b_kc) layout_ok = g.c_bf16 && g.act == ACT_NONE && !g.ct;
+  }
+  const bool big = g.splits == 1 && (g.M % G_BM) == 0 && (g.N % G_BN) == 0 && (g.K % G_BK) == 0 && g.K > 0 && vec_ok &&
+                   (g.c_bf16 || (g.act == ACT_NONE && !g.mask)) &&  // fp32 + act / act' epilogues: any-layout kernel
+                   layout_ok;
+  // transposed copy / column partials / activity bits: the any-layout kernel has none of them
+  if (!big) return (g.ct || g.colpart || g.bits) ? GEMM_REFUSE : GEMM_ANY;
+  if (!g.c_bf16 && g.ct) return GEMM_REFUSE;            // C^T is a bf16 epilogue
+  if (g.dact && g.act != ACT_NONE) return GEMM_REFUSE;  // one kernel applies act or act', not both
+  // skinny K with a bf16 output: the store-stream kernel (see gemm_k64_kernel)
+  return nt && g.c_bf16 && (g.K == 64 || g.K == 128) && g.beta == 0.f ? GEMM_K64 : GEMM_256;
+}
+
+template <int A_KC, int B_KC>
+static int any_launch(const GemmArgs& g, hipStream_t st) {
+  constexpr auto kern = gemm_kernel<A_KC, B_KC>;
+  lds_limit_once<kern, LDS_BYTES>();
+  const int grid = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+  hipLaunchKernelGGL(kern, dim3(grid, g.splits), dim3(NT), LDS_BYTES, st, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.c_bf16,
+                     g.M, g.N, g.K, g.bias, g.act, g.mask, g.ldm, g.dact, g.alpha, g.beta, g.kstep, g.c_split);
+  return 0;
+}
+
+static int gemm_impl(const GemmArgs& g, hipStream_t stream) {
+  if (!g.A || !g.B || !g.C || g.M < 0 || g.N < 0 || g.K < 0 || g.act < 0 || g.act > 3) return EM_ERR_ARG;
+  if (g.mask && (g.dact < 1 || g.dact > 3)) return EM_ERR_ARG;
+  // ReLU activity bits (see relu_bits_*): written by a bf16 forward with act relu, read instead of the
+  // saved activation by a relu dgrad; 256-tile / skinny-K paths only, M a multiple of 32
+  if (g.bits) {
+    const bool wr = g.act == ACT_RELU && !g.mask && g.dact == 0;
+    const bool rd = g.act == ACT_NONE && !g.mask && g.dact == ACT_RELU;
+    if (!(wr || rd) || !g.c_bf16 || (g.M & 31) || ((uintptr_t)g.bits & 3)) return EM_ERR_ARG;
+  } else if (g.dact && !g.mask) {
+    return EM_ERR_ARG;
+  }
+  if ((uintptr_t)g.colpart & 3) return EM_ERR_ARG;
+  if (g.M == 0 || g.N == 0) return 0;
+  // 16-byte vector loads need 8-element-aligned leading dimensions and base pointers
+  if ((g.lda & 7) || (g.ldb & 7) || (((uintptr_t)g.A) & 15) || (((uintptr_t)g.B) & 15)) return EM_ERR_ARG;
+  int rc;
+  switch (gemm_route(g)) {
+    case GEMM_K64: rc = k64_dispatch(g, stream); break;
+    case GEMM_256: rc = g_dispatch(g, stream); break;
+    case GEMM_ANY:
+      rc = g.a_kc ? (g.b_kc ? any_launch<1, 1>(g, stream) : any_launch<1, 0>(g, stream))
+                  : (g.b_kc ? any_launch<0, 1>(g, stream) : any_launch<0, 0>(g, stream));
+      break;
+    default: return EM_ERR_ARG;
+  }
+  if (rc) return rc;
+  EM_CHECK_LAUNCH();
+  return 0;
+}
+
+// C = epi(alpha * A B) as described in the header.  Optional, 256-tile / skinny-K paths only:
+//   ct       bf16 [N][M], a transposed copy of a bf16 output;
+//   colpart  fp32 [M / 128][N] column sums of the epilogue (K3 bias gradient, fused): row p = sum over output
+//            rows 128p .. 128p + 127 of the final epilogue values (after act' for dgrad), before the bf16
+//            rounding; em_colpart_reduce sums them;
+//   bits     ReLU activity bits, uint32 [M / 32][N], bit m & 31 of word (m >> 5) * N + n = output[m][n] > 0:
+//            written when act is relu, read in place of the saved activation when dact is relu and mask is
+//            null (64x less traffic than the bf16 activation).
 EM_API int em_gemm_bf16(const void* A, int64_t lda, int a_kc, const void* B, int64_t ldb, int b_kc, void* C,
                         int64_t ldc, int c_bf16, int M, int N, int K, const float* bias, int act, const void* mask,
-                        int64_t ldm, int dact, float alpha, float beta, void* ct, int64_t ldct, hipStream_t stream) {
-  return gemm_impl(A, lda, a_kc, B, ldb, b_kc, C, ldc, c_bf16, M, N, K, bias, act, mask, ldm, dact, alpha, beta, ct,
-                   ldct, 1, K, 0, stream);
-}
-
-// The same GEMM on the 256-tile path with the epilogue's column sums (K3 bias gradient, fused): colpart
-// receives fp32 [M / 128][N] partials -- row p = sum over output rows 128p .. 128p + 127 of the final
-// epilogue values (after act' for dgrad), before the bf16 rounding.  em_colpart_reduce sums them.
-EM_API int em_gemm_bf16_cs(const void* A, int64_t lda, int a_kc, const void* B, int64_t ldb, int b_kc, void* C,
-                           int64_t ldc, int c_bf16, int M, int N, int K, const float* bias, int act, const void* mask,
-                           int64_t ldm, int dact, float alpha, float beta, void* ct, int64_t ldct, float* colpart,
-                           hipStream_t stream) {
-  if (!colpart || ((uintptr_t)colpart & 3)) return EM_ERR_ARG;
-  return gemm_impl(A, lda, a_kc, B, ldb, b_kc, C, ldc, c_bf16, M, N, K, bias, act, mask, ldm, dact, alpha, beta, ct,
-                   ldct, 1, K, 0, stream, colpart);
-}
-
-// The general form: optional column partials (as em_gemm_bf16_cs) and ReLU activity bits (uint32
-// [M / 32][N], bit m & 31 of word (m >> 5) * N + n = output[m][n] > 0): written when act is relu,
-// read in place of the saved activation when dact is relu and mask is null (64x less traffic than
-// the bf16 activation).
-EM_API int em_gemm_bf16_ex(const void* A, int64_t lda, int a_kc, const void* B, int64_t ldb, int b_kc, void* C,
-                           int64_t ldc, int c_bf16, int M, int N, int K, const float* bias, int act, const void* mask,
-                           int64_t ldm, int dact, float alpha, float beta, void* ct, int64_t ldct, float* colpart,
-                           uint32_t* bits, hipStream_t stream) {
-  if ((uintptr_t)colpart & 3) return EM_ERR_ARG;
-  return gemm_impl(A, lda, a_kc, B, ldb, b_kc, C, ldc, c_bf16, M, N, K, bias, act, mask, ldm, dact, alpha, beta, ct,
-                   ldct, 1, K, 0, stream, colpart, bits);
+                        int64_t ldm, int dact, float alpha, float beta, void* ct, int64_t ldct, float* colpart,
+                        uint32_t* bits, hipStream_t stream) {
+  return gemm_impl({(const __bf16*)A, lda, a_kc, (const __bf16*)B, ldb, b_kc, C, ldc, c_bf16, M, N, K, bias, act,
+                    (const __bf16*)mask, ldm, dact, alpha, beta, (__bf16*)ct, ldct, 1, K, 0, colpart, bits},
+                   stream);
 }
 
 // Split-K on the any-layout kernel: `splits` slices of `kstep` (multiple of 64) along K, slice s writing
@@ -1352,76 +1342,9 @@ EM_API int em_gemm_bf16_splitk(const void* A, int64_t lda, int a_kc, const void*
                                int64_t c_split, hipStream_t stream) {
   if (splits < 1 || splits > 65535 || kstep <= 0 || (kstep & 63) || (int64_t)splits * kstep < K || c_split < 0)
     return EM_ERR_ARG;
-  return gemm_impl(A, lda, a_kc, B, ldb, b_kc, C, ldc, c_bf16, M, N, K, nullptr, 0, nullptr, 0, 0, alpha, 0.f,
-                   nullptr, 0, splits, kstep, c_split, stream);
-}
-
-static int gemm_impl(const void* A, int64_t lda, int a_kc, const void* B, int64_t ldb, int b_kc, void* C,
-                     int64_t ldc, int c_bf16, int M, int N, int K, const float* bias, int act, const void* mask,
-                     int64_t ldm, int dact, float alpha, float beta, void* ct, int64_t ldct, int splits, int kstep,
-                     int64_t c_split, hipStream_t stream, float* colpart, uint32_t* bits) {
-  if (!A || !B || !C || M < 0 || N < 0 || K < 0 || act < 0 || act > 3) return EM_ERR_ARG;
-  if (mask && (dact < 1 || dact > 3)) return EM_ERR_ARG;
-  // ReLU activity bits (see relu_bits_*): written by a bf16 forward with act relu, read instead of the
-  // saved activation by a relu dgrad; 256-tile / skinny-K paths only, M a multiple of 32
-  if (bits) {
-    const bool wr = act == ACT_RELU && !mask && dact == 0, rd = act == ACT_NONE && !mask && dact == ACT_RELU;
-    if (!(wr || rd) || !c_bf16 || (M & 31) || ((uintptr_t)bits & 3)) return EM_ERR_ARG;
-  } else if (dact && !mask) {
-    return EM_ERR_ARG;
-  }
-  if (M == 0 || N == 0) return 0;
-  // 16-byte vector loads need 8-element-aligned leading dimensions and base pointers
-  if ((lda & 7) || (ldb & 7) || (((uintptr_t)A) & 15) || (((uintptr_t)B) & 15)) return EM_ERR_ARG;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr = true;
-  }
-  // the 256-tile and skinny-K epilogues store bf16 C and C^T rows, and load the act' mask, as 16-byte
-  // vectors: a bf16 output (mask, C^T) that is not 16-byte aligned with an 8-element leading dimension
-  // takes the any-layout kernel's scalar epilogue (which has no C^T / colpart / bits: EM_ERR_ARG below)
-  const bool vec_ok = !c_bf16 || ((((uintptr_t)C & 15) == 0 && (ldc & 7) == 0) &&
-                                  (!mask || (((uintptr_t)mask & 15) == 0 && (ldm & 7) == 0)) &&
-                                  (!ct || (((uintptr_t)ct & 15) == 0 && (ldct & 7) == 0)));
-  const bool big = splits == 1 && (M % G_BM) == 0 && (N % G_BN) == 0 && (K % G_BK) == 0 && K > 0 &&
-                   (((uintptr_t)A | (uintptr_t)B) & 15) == 0 && vec_ok &&
-                   (c_bf16 || (act == ACT_NONE && !mask)) &&  // fp32 + act / act' epilogues: any-layout kernel
-                   g_layout_ok(a_kc, b_kc, c_bf16, act, mask, dact, ct, bits, lda, ldb, K);
-  // skinny K (64 / 128) with a bf16 output: the store-stream kernel (see gemm_k64_kernel)
-  if (big && a_kc && b_kc && c_bf16 && (K == 64 || K == 128) && beta == 0.f) {
-    const int rc = k64_dispatch(stream, (const __bf16*)A, lda, (const __bf16*)B, ldb, (__bf16*)C, ldc, (__bf16*)ct,
-                                ldct, M, N, K, bias, act, (const __bf16*)mask, ldm, dact, alpha, colpart, bits);
-    if (rc) return rc;
-    EM_CHECK_LAUNCH();
-    return 0;
-  }
-  if (big) {
-    const int rc = g_dispatch(dim3((M / G_BM) * (N / G_BN)), stream, a_kc, b_kc, (const __bf16*)A, lda,
-                              (const __bf16*)B, ldb, C, ldc, c_bf16, (__bf16*)ct, ldct, M, N, K, bias, act, (const __bf16*)mask, ldm, dact, alpha,
-                              beta, colpart, bits);
-    if (rc) return rc;
-    EM_CHECK_LAUNCH();
-    return 0;
-  }
-  if (ct || colpart || bits) return EM_ERR_ARG;  // transposed copy / column partials / bits: 256 path only
-  const int grid = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  const __bf16* a = (const __bf16*)A;
-  const __bf16* b = (const __bf16*)B;
-  const __bf16* mk = (const __bf16*)mask;
-#define EM_GEMM_LAUNCH(AK, BKC)                                                                                        \
-  hipLaunchKernelGGL((gemm_kernel<AK, BKC>), dim3(grid, splits), dim3(NT), LDS_BYTES, stream, a, lda, b, ldb, C, ldc,   \
-                     c_bf16, M, N, K, bias, act, mk, ldm, dact, alpha, beta, kstep, c_split)
-  if (a_kc && b_kc) EM_GEMM_LAUNCH(1, 1);
-  else if (a_kc && !b_kc) EM_GEMM_LAUNCH(1, 0);
-  else if (!a_kc && !b_kc) EM_GEMM_LAUNCH(0, 0);
-  else EM_GEMM_LAUNCH(0, 1);
-#undef EM_GEMM_LAUNCH
-  EM_CHECK_LAUNCH();
-  return 0;
+  return gemm_impl({(const __bf16*)A, lda, a_kc, (const __bf16*)B, ldb, b_kc, C, ldc, c_bf16, M, N, K, nullptr, 0,
+                    nullptr, 0, 0, alpha, 0.f, nullptr, 0, splits, kstep, c_split, nullptr, nullptr},
+                   stream);
 }
 
 EM_API int em_transpose_bf16(const void* src, int64_t ld_src, int R, int Cc, void* dst, int64_t ld_dst,
@@ -1454,7 +1377,7 @@ EM_API int em_colsum_bf16(const void* X, int64_t ldx, int M, int N, float* out, 
   return 0;
 }
 
-// out[n] (+)= scale * sum_p part[p][n], fixed order (the em_gemm_bf16_cs bias-gradient partials)
+// out[n] (+)= scale * sum_p part[p][n], fixed order (em_gemm_bf16's colpart bias-gradient partials)
 EM_API int em_colpart_reduce(const float* part, int nparts, int N, float* out, int accumulate, float scale,
                              hipStream_t stream) {
   if (!part || !out || nparts < 0 || N < 0) return EM_ERR_ARG;
@@ -1487,11 +1410,7 @@ EM_API int em_wgrad_skinny(const void* P, int64_t ldp, const void* Q, int64_t ld
       (((uintptr_t)P | (uintptr_t)Q) & 15))
     return EM_ERR_ARG;
   if ((int64_t)kstep * ldq * 2 >= (1ll << 31) || (int64_t)kstep * ldp * 2 >= (1ll << 31)) return EM_ERR_ARG;  // 32-bit offsets
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)wgrad_skinny_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SK_LDS);
-    attr = true;
-  }
+  lds_limit_once<wgrad_skinny_kernel, SK_LDS>();
   hipLaunchKernelGGL(wgrad_skinny_kernel, dim3(W / SK_WT, splits), dim3(256), SK_LDS, stream, (const __bf16*)P, ldp,
                      (const __bf16*)Q, ldq, K, W, kstep, part);
   EM_CHECK_LAUNCH();

@@ -16,6 +16,7 @@
 // (four consecutive k for K-contiguous operands, four consecutive rows otherwise).  Split-K over
 // gridDim.y writes slice s of the K range to C + s*c_split (summed by the caller) so the wgrad of
 // a small layer over a large batch still fills the chip.  Block ids are XCD-remapped like gemm.hip.
+#include "act.h"
 #include "common.h"
 
 namespace {
@@ -25,26 +26,7 @@ constexpr int FROW = FBM + 4;                      // floats per staged k row (p
 constexpr int FTILE = FBK * FROW * 4;              // bytes per operand per stage
 constexpr int F_LDS = 2 * 2 * FTILE;
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2, ACT_TANH = 3 };
-
 EM_DEVICE f32x16 mfma32_f32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-EM_DEVICE float f_act(float x, int act) {
-  switch (act) {
-    case ACT_RELU: return fmaxf(x, 0.f);
-    case ACT_SIGMOID: return 1.f / (1.f + __expf(-x));
-    case ACT_TANH: return tanhf(x);
-    default: return x;
-  }
-}
-EM_DEVICE float f_dact(float y, int act) {  // derivative expressed through the saved output y
-  switch (act) {
-    case ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case ACT_SIGMOID: return y * (1.f - y);
-    case ACT_TANH: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
 
 // 128 rows x 16 k of one operand: 512 float4 pieces, 2 per thread, zero-filled out of range
 template <int KC>
@@ -100,11 +82,6 @@ EM_DEVICE void f_store(char* lds, int tid, const f32x4 (&v)[2]) {
   }
 }
 
-EM_DEVICE int f_xcd_remap(int bid, int nwg) {
-  const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-}
-
 template <int A_KC, int B_KC>
 __global__ void __launch_bounds__(FNT, 2)
 gemm_f32_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
@@ -117,7 +94,7 @@ gemm_f32_kernel(const float* __restrict__ A, int64_t lda, const float* __restric
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int tiles_n = (N + FBN - 1) / FBN, tiles_m = (M + FBM - 1) / FBM;
-  const int bid = f_xcd_remap(blockIdx.x, tiles_m * tiles_n);
+  const int bid = xcd_remap(blockIdx.x, tiles_m * tiles_n);
   const int m0 = (bid / tiles_n) * FBM, n0 = (bid % tiles_n) * FBN;
   const int kb = blockIdx.y * kstep, ke = min(K, kb + kstep);
   C += (int64_t)blockIdx.y * c_split;
@@ -182,9 +159,9 @@ gemm_f32_kernel(const float* __restrict__ A, int64_t lda, const float* __restric
         if (row >= M) continue;
         float v = alpha * acc[i][j][g];
         if (dact) {
-          v *= f_dact(Y[(int64_t)row * ldy + col], act);
+          v *= act_dfn(Y[(int64_t)row * ldy + col], act, true);
         } else {
-          v = f_act(v + bv, act);
+          v = act_fn(v + bv, act);
         }
         float* cp = C + (int64_t)row * ldc + col;
         v = beta != 0.f ? v + beta * *cp : v;

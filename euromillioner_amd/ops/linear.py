@@ -26,17 +26,11 @@ ACTS = {"none": 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 N.register_signatures({
     "em_gemm_bf16": (N._i32, [N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64, N._i32,
                               N._i32, N._i32, N._i32, N._c_void_p, N._i32, N._c_void_p, N._i64, N._i32, N._f32, N._f32,
-                              N._c_void_p, N._i64, N._c_void_p]),
+                              N._c_void_p, N._i64, N._c_void_p, N._c_void_p, N._c_void_p]),
     "em_gemm_bf16_splitk": (N._i32, [N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64,
                                      N._i32, N._i32, N._i32, N._i32, N._f32, N._i32, N._i32, N._i64, N._c_void_p]),
     "em_wgrad_skinny": (N._i32, [N._c_void_p, N._i64, N._c_void_p, N._i64, N._i32, N._i32, N._i32, N._c_void_p,
                                  N._i64, N._i32, N._f32, N._f32, N._c_void_p, N._i32, N._i32, N._c_void_p]),
-    "em_gemm_bf16_cs": (N._i32, [N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64,
-                                 N._i32, N._i32, N._i32, N._i32, N._c_void_p, N._i32, N._c_void_p, N._i64, N._i32,
-                                 N._f32, N._f32, N._c_void_p, N._i64, N._c_void_p, N._c_void_p]),
-    "em_gemm_bf16_ex": (N._i32, [N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64, N._i32, N._c_void_p, N._i64,
-                                 N._i32, N._i32, N._i32, N._i32, N._c_void_p, N._i32, N._c_void_p, N._i64, N._i32,
-                                 N._f32, N._f32, N._c_void_p, N._i64, N._c_void_p, N._c_void_p, N._c_void_p]),
     "em_colpart_reduce": (N._i32, [N._c_void_p, N._i32, N._i32, N._c_void_p, N._i32, N._f32, N._c_void_p]),
     "em_colsum_ws_floats": (N._i32, [N._i32, N._i32]),
     "em_colsum_bf16": (N._i32, [N._c_void_p, N._i64, N._i32, N._i32, N._c_void_p, N._i32, N._f32, N._c_void_p,
@@ -89,7 +83,7 @@ def big_ok(M: int, N_: int, K: int) -> bool:
 
 def big_mn_ok(t: torch.Tensor, K: int) -> bool:
     """An MN-contiguous operand ([K, rows] storage) on the 256-tile path: 32-bit buffer offsets over K rows
-    (``g_layout_ok`` in csrc/gemm.hip)."""
+    (``gemm_route`` in csrc/gemm.hip)."""
     return K * t.stride(0) * 2 < (1 << 31)
 
 
@@ -124,13 +118,13 @@ def gemm(a: torch.Tensor, a_kc: bool, b: torch.Tensor, b_kc: bool, out: torch.Te
         if tuple(dact_src.shape) != (M, N_) or dact_src.stride(1) != 1:
             raise ValueError("dact_src must be bf16 [M, N] with unit column stride")
         ldm = dact_src.stride(0)
+    tile256 = a_kc and big_ok(M, N_, K) and (b_kc or big_mn_ok(b, K))  # the path with colpart / bits epilogues
     read_bits = bits is not None and dact_src is None and dact == "relu" and act in ("none", "identity")
     if bits is not None:
         N.check_cuda(bits, "bits", torch.int32)
         if not (read_bits or (act == "relu" and dact_src is None)):
             raise ValueError("bits: written by act='relu' or read by dact='relu' without dact_src")
-        if (out.dtype != torch.bfloat16 or not (a_kc and big_ok(M, N_, K) and (b_kc or big_mn_ok(b, K)))
-                or tuple(bits.shape) != (M // 32, N_)):
+        if out.dtype != torch.bfloat16 or not tile256 or tuple(bits.shape) != (M // 32, N_):
             raise ValueError("bits need the 256-tile path (A K-contiguous), a bf16 output and an int32 [M / 32, N] "
                              "buffer")
     if ct is not None:
@@ -138,22 +132,14 @@ def gemm(a: torch.Tensor, a_kc: bool, b: torch.Tensor, b_kc: bool, out: torch.Te
         if not (a_kc and b_kc and big_ok(M, N_, K)) or tuple(ct.shape) != (N_, M) or not is_aligned(ct):
             raise ValueError("ct needs the 256-tile NT path and an aligned bf16 [N, M] buffer")
     args = (a.data_ptr(), a.stride(0), int(a_kc), b.data_ptr(), b.stride(0), int(b_kc),
-            out.data_ptr(), out.stride(0), int(out.dtype == torch.bfloat16), M, N_, K,
-            bias.data_ptr() if bias is not None else None, ACTS[act],
-            dact_src.data_ptr() if dact_src is not None else None, ldm,
-            ACTS[dact] if (dact_src is not None or read_bits) else 0,
-            float(alpha), float(beta), ct.data_ptr() if ct is not None else None, ct.stride(0) if ct is not None else 0)
+            out.data_ptr(), out.stride(0), int(out.dtype == torch.bfloat16), M, N_, K, N.ptr(bias), ACTS[act],
+            N.ptr(dact_src), ldm, ACTS[dact] if (dact_src is not None or read_bits) else 0,
+            float(alpha), float(beta), N.ptr(ct), ct.stride(0) if ct is not None else 0)
     if colpart is not None:
         N.check_cuda(colpart, "colpart", torch.float32)
-        if not (a_kc and big_ok(M, N_, K) and (b_kc or big_mn_ok(b, K))) or colpart.numel() < (M // 128) * N_:
+        if not tile256 or colpart.numel() < (M // 128) * N_:
             raise ValueError("colpart needs the 256-tile path (A K-contiguous) and M / 128 * N floats")
-    if bits is not None:
-        N.call("em_gemm_bf16_ex", *args, colpart.data_ptr() if colpart is not None else None, bits.data_ptr(),
-               N.stream_handle(out.device))
-    elif colpart is not None:
-        N.call("em_gemm_bf16_cs", *args, colpart.data_ptr(), N.stream_handle(out.device))
-    else:
-        N.call("em_gemm_bf16", *args, N.stream_handle(out.device))
+    N.call("em_gemm_bf16", *args, N.ptr(colpart), N.ptr(bits), N.stream_handle(out.device))
     return out
 
 
@@ -195,6 +181,14 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, act:
     return gemm(x, True, w, True, out, M, N_, K, bias=bias, act=act, ct=ct, bits=bits)
 
 
+def _dgrad_act_src(y_prev, dact: str, bits):
+    """The (``dact_src``, ``bits``) a dgrad hands to :func:`gemm`: neither without an activation, and the
+    activity bits, when given, in place of y_prev."""
+    if dact in ("none", "identity"):
+        return None, None
+    return (None, bits) if bits is not None else (y_prev, None)
+
+
 def linear_dgrad_nt(dz: torch.Tensor, wt: torch.Tensor, y_prev: torch.Tensor | None = None, dact: str = "relu",
                     out: torch.Tensor | None = None, ct: torch.Tensor | None = None,
                     colpart: torch.Tensor | None = None, bits: torch.Tensor | None = None) -> torch.Tensor:
@@ -205,10 +199,7 @@ def linear_dgrad_nt(dz: torch.Tensor, wt: torch.Tensor, y_prev: torch.Tensor | N
     K = wt.shape[0]
     if out is None:
         out = empty_aligned(M, K, torch.bfloat16, dz.device)
-    if dact in ("none", "identity"):
-        y_prev = bits = None
-    if bits is not None:
-        y_prev = None
+    y_prev, bits = _dgrad_act_src(y_prev, dact, bits)
     return gemm(dz, True, wt, True, out, M, K, N_, dact_src=y_prev, dact=dact, ct=ct, colpart=colpart, bits=bits)
 
 
@@ -233,10 +224,7 @@ def linear_dgrad(dz: torch.Tensor, w: torch.Tensor, y_prev: torch.Tensor | None 
     K = w.shape[1]
     if out is None:
         out = empty_aligned(M, K, torch.bfloat16, dz.device)
-    if dact in ("none", "identity"):
-        y_prev = bits = None
-    if bits is not None:
-        y_prev = None
+    y_prev, bits = _dgrad_act_src(y_prev, dact, bits)
     if big_ok(M, K, N_) and is_aligned(dz):
         # 256-tile shapes: transpose the (weight-sized) w once and take the NT path.  Reading w in place
         # (the kernel's MN-operand form, gemm(..., b_kc=False)) measured slower: 7.49 vs 6.72 ms at
