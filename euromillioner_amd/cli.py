@@ -11,6 +11,7 @@ runs the whole pipeline (``Main.java:35``).  Here:
     euromillioner train --model counts --ckpt base.cnt     # the transition-count baseline every model is read against
     euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv] [--tickets 5 --temperature 1.0]
     euromillioner backtest --ckpt model.zip --tickets 16   # prize tiers of sampled tickets on the validation split
+    euromillioner evaluate --ckpt model.zip|.cnt|.npz|.json   # validation metrics + reliability table, Brier score, ECE
     euromillioner explain --ckpt model.json [--top 3]      # which of the last draw's numbers push each GBDT pick (TreeSHAP)
     euromillioner explain --ckpt forest.npz [--top 3]      # the same for a forest checkpoint, over its last `lags` draws
     euromillioner gen --n 1000000 --planted 0.9 --out draws.csv
@@ -57,6 +58,7 @@ _FLAGS = {
     "--profile-dir": "log.profile_dir", "--profile-steps": "log.profile_steps",
     "--tickets": "tickets.n", "--temperature": "tickets.temperature", "--ticket-seed": "tickets.seed",
     "--ckpt": "ckpt.path", "--resume": "ckpt.resume", "--ckpt-every": "ckpt.every",
+    "--edges": "eval.edges",
     "--log-level": "log.level", "--device": "device",
 }
 
@@ -96,6 +98,9 @@ def build_parser() -> argparse.ArgumentParser:
     p = sub.add_parser("backtest", help="play sampled tickets on every validation draw and count prize tiers")
     _add_common(p)
     p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "counts"])
+    p = sub.add_parser("evaluate", help="score any checkpoint on the validation split: draw metrics + calibration report")
+    _add_common(p)
+    p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "rf", "gbdt", "counts"])
     p = sub.add_parser("explain", help="TreeSHAP: the features behind each number a GBDT (.json) or forest (.npz) checkpoint picks")
     _add_common(p)
     p.add_argument("--top", type=int, default=3, help="features listed per picked number")
@@ -172,6 +177,10 @@ def main(argv=None) -> int:
             from .train import backtest
 
             res = backtest(cfg)
+        elif a.cmd == "evaluate":
+            from .train import evaluate
+
+            res = evaluate(cfg, model=a.model)
         elif a.cmd == "explain":
             from .train import explain_next
 

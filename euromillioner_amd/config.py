@@ -155,6 +155,11 @@ class TicketConfig:
 
 
 @dataclasses.dataclass
+class EvalConfig:
+    edges: str | None = None  # evaluate: comma list of up to 15 ascending probability edges (None: calibration.DEFAULT_EDGES)
+
+
+@dataclasses.dataclass
 class RunConfig:
     data: DataConfig = dataclasses.field(default_factory=DataConfig)
     gbdt: GBDTConfig = dataclasses.field(default_factory=GBDTConfig)
@@ -165,6 +170,7 @@ class RunConfig:
     ckpt: CkptConfig = dataclasses.field(default_factory=CkptConfig)
     log: LogConfig = dataclasses.field(default_factory=LogConfig)
     tickets: TicketConfig = dataclasses.field(default_factory=TicketConfig)
+    eval: EvalConfig = dataclasses.field(default_factory=EvalConfig)
     model: str = "gbdt"  # gbdt | rf | mlp | mlp-wide | counts
     device: str = "auto"
     reference_compat: bool = False  # reproduce D-f (second booster trained on validation) + checkPredicts

@@ -1041,3 +1041,202 @@ def _backtest_report(head: dict, r: dict, rows: int, tc) -> dict:
     return {**head, "rows": rows, "tickets": r["tickets"], "n_tickets": tc.n, "temperature": tc.temperature, "seed": tc.seed,
             "hist": r["hist"].tolist(), "best": r["best"].tolist(), "tiers": tiers.tolist(),
             "uniform": {k: np.asarray(v).tolist() for k, v in r["uniform"].items()}}
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluate: any checkpoint on the validation split, with a calibration report
+# ---------------------------------------------------------------------------------------------
+def _eval_edges(cfg: RunConfig) -> tuple:
+    """``eval.edges``: None (the default edges) or a comma list of probabilities."""
+    from . import calibration as CAL
+
+    e = cfg.eval.edges
+    if e is None:
+        return CAL.DEFAULT_EDGES
+    if isinstance(e, (int, float)):
+        e = (e,)
+    elif isinstance(e, str):
+        try:
+            e = tuple(float(p) for p in e.split(",") if p.strip())
+        except ValueError as err:
+            raise ValueError(f"eval.edges={cfg.eval.edges!r}: a comma list of probabilities ({err})") from err
+    return CAL.check_edges(e)
+
+
+def _evaluate_numpy(logits_of, targets: np.ndarray, a: int, b: int, loss: str, edges, chunk: int = 1 << 14) -> dict:
+    """The ``--device cpu`` engine: ``logits_of(c0, c1)`` gives the [c1 - c0, >= 62] logits of samples [c0, c1), which
+    are scored against the masks ``targets[c0:c1]`` by ``metrics.draw_metrics`` and ``calibration.calibration_np``."""
+    from . import calibration as CAL
+    from .metrics import draw_metrics
+    from .models.count_table import _bits
+
+    keys = ("loss", "acc", "acc_thr", "hits_main", "hits_star", "exact", "trivial_acc")
+    tot, totals = np.zeros(len(keys), dtype=np.float64), None
+    for c0 in range(a, b, chunk):
+        c1 = min(b, c0 + chunk)
+        z = np.asarray(logits_of(c0, c1))[:, :62]
+        tm = targets[c0:c1]
+        r = draw_metrics(z.astype(np.float64), _bits(tm.view(np.uint64))[:, :62], loss)
+        tot += np.array([r[k] for k in keys]) * (c1 - c0)
+        totals = CAL.add_totals(totals, CAL.calibration_np(z, tm, loss, edges))
+    val = {k: float(tot[i] / (b - a)) for i, k in enumerate(keys)}
+    val["count"] = int(b - a)
+    return {"val": val, "calibration": CAL.report(totals, b - a, loss, edges)}
+
+
+def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
+    """``euromillioner evaluate``: score a checkpoint of any of the five model kinds on the positional validation
+    split (the kind is read from the checkpoint; ``model``, the CLI's ``--model``, must agree with it when given): the draw metrics of ``train`` plus a calibration report (reliability table per group, Brier score,
+    expected calibration error; :mod:`euromillioner_amd.calibration`).  On a GPU the logits stay on the device
+    (``ops.calibration``); ``--device cpu`` runs the numpy specification on the model's host logits."""
+    from . import calibration as CAL
+    from .data.draws import mask_bits
+
+    path = cfg.ckpt.resume or cfg.ckpt.path
+    if not path:
+        raise ValueError("evaluate needs --ckpt pointing at a checkpoint")
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    kind = {".npz": "rf", ".json": "gbdt", ".cnt": "counts"}.get(os.path.splitext(path)[1], "mlp")
+    if model is not None and {"mlp-wide": "mlp"}.get(model, model) != kind:
+        raise ValueError(f"--model {model} was asked for, {os.path.basename(path)} is a {kind} checkpoint")
+    edges = _eval_edges(cfg)
+    use_gpu = cfg.device == "cuda" or (cfg.device == "auto" and torch.cuda.is_available())
+    ds = load_draws(cfg)
+    host_masks = mask_bits(ds.numbers).view(np.int64)
+    head: dict = {"checkpoint": path, "engine": "hip" if use_gpu else "numpy"}
+
+    def split(lags: int) -> tuple[int, int]:
+        n = len(ds) - lags
+        margin = positional_split(n, cfg.data.train_pct) if n > 0 else 0
+        if n - margin < 1:
+            raise ValueError("empty validation split")
+        return margin, n
+
+    def device_masks():
+        from .models.mlp import FusedSmallMLP
+
+        return FusedSmallMLP.prepare(ds.numbers)
+
+    if path.endswith(".npz"):
+        from .models.forest import RandomForest, pack_bits
+
+        rf = RandomForest.load(path)
+        lags = int(rf.F) // 62
+        if lags < 1 or int(rf.F) != 62 * lags:
+            raise ValueError(f"evaluate needs a next-draw forest over 62 features per draw, this checkpoint has {rf.F}")
+        margin, n = split(lags)
+        loss = "bce"
+        head.update(model="rf", lags=lags, trees=int(len(rf.feat)))
+        if use_gpu:
+            from .ops import calibration as OC
+            from .ops import tree_inputs as TI
+
+            masks = device_masks()
+            tgt = masks[lags - 1:] if lags > 1 else masks  # as pipeline.device_draw_metrics
+
+            def logits_of(b, o, si):
+                return rf.predict_proba_device(TI.rf_rows(masks, lags, first=o, count=b)[0], out_logit=True)
+
+            res = OC.calibrate_logits(logits_of, tgt, n - margin, loss, edges, offset=margin)
+        else:
+            X, _ = lag_features(ds.numbers, lags)
+
+            def logits_np_of(c0, c1):
+                p = rf.predict_proba(pack_bits(X[c0:c1]))
+                return torch.logit(torch.from_numpy(p).double().clamp(1e-7, 1 - 1e-7)).float().numpy()  # as train_rf
+
+            res = _evaluate_numpy(logits_np_of, host_masks[lags:], margin, n, loss, edges)
+    elif path.endswith(".json"):
+        from .data.draws import featurize_raw
+        from .models.gbdt import GBDT
+        from .models.gbdt_explain import num_features
+
+        g = GBDT.load(path)
+        if g.n_tasks != 62 or g.objective not in ("reg:logistic", "binary:logistic"):
+            raise ValueError(f"evaluate needs a 62-booster logistic next-draw GBDT; this checkpoint has {g.n_tasks} "
+                             f"booster(s) with objective {g.objective}")
+        nf = num_features(g)
+        margin, n = split(1)
+        loss = "bce"
+        head.update(model="gbdt", features=nf)
+
+        def host_margin(c0, c1):
+            x = multi_hot(ds.numbers[c0:c1]).astype(np.float64)
+            if nf > 62 and ds.dates is not None:
+                x = np.concatenate([x, featurize_raw(ds)[c0:c1, :4].astype(np.float64)], axis=1)
+            if x.shape[1] != nf:
+                raise ValueError(f"the checkpoint expects {nf} features, the data gives {x.shape[1]}")
+            return g.predict_margin(x)
+
+        if use_gpu:
+            from .ops import calibration as OC
+
+            masks = device_masks()
+            if nf == 62:
+                def logits_of(b, o, si):
+                    return g.predict_margin_draw_masks(masks, (o, o + b))
+            else:  # date columns: the margins of the host rows, uploaded as [rows, 64]
+                def logits_of(b, o, si):
+                    z = torch.zeros(b, 64, dtype=torch.float32)
+                    z[:, :62] = torch.from_numpy(np.asarray(host_margin(o, o + b), dtype=np.float32))
+                    return z.cuda()
+
+            res = OC.calibrate_logits(logits_of, masks, n - margin, loss, edges, offset=margin)
+        else:
+            res = _evaluate_numpy(host_margin, host_masks[1:], margin, n, loss, edges)
+    elif path.endswith(".cnt"):
+        from .models.count_table import CountTable
+
+        ct = CountTable.load(path, "cuda" if use_gpu else "cpu")
+        margin, n = split(ct.lags)
+        loss = "softmax"
+        head.update(model="counts", lags=ct.lags)
+        if use_gpu:
+            from .ops import calibration as OC
+
+            masks = device_masks()
+            res = OC.calibrate_model(ct, masks, n - margin, loss, edges, offset=margin, target_masks=ct._tmasks(masks))
+        else:
+            res = _evaluate_numpy(lambda c0, c1: ct.logits_np(host_masks, np.arange(c0, c1)), host_masks[ct.lags:],
+                                  margin, n, loss, edges)
+    else:
+        from .models.mlp import DrawMLP
+
+        ck = load_mlp_checkpoint(path)
+        sizes, ex = tuple(ck["sizes"]), ck["extra"]
+        lags = int(ex.get("lags", sizes[0] // 62))
+        act, loss = ex.get("activation", "relu"), ex.get("loss", "softmax")
+        margin, n = split(lags)
+        head.update(model="mlp", sizes=list(sizes), lags=lags)
+        if use_gpu:
+            from .models.mlp import FusedSmallMLP
+            from .ops import calibration as OC
+
+            masks = device_masks()
+            if sizes == (62, 128, 62) and act == "relu":
+                model = FusedSmallMLP("cuda", loss=loss, dtype=cfg.mlp.dtype,
+                                      state_dict={_FusedEngine._MAP[k]: v for k, v in ck["state_dict"].items()})
+                tgt = None
+            else:
+                from .models.gemm_mlp import GemmMLPTrainer
+
+                model = GemmMLPTrainer(sizes, "cuda", activation=act, loss=loss, state_dict=ck["state_dict"],
+                                       dtype=cfg.mlp.dtype, lags=lags)
+                tgt = model._tmasks(masks)
+            res = OC.calibrate_model(model, masks, n - margin, loss, edges, offset=margin, chunk=1 << 16,
+                                     target_masks=tgt)
+        else:
+            net = DrawMLP(sizes, activation=act, loss=loss, use_hip=False)
+            net.load_state_dict(ck["state_dict"])
+            X, _ = lag_features(ds.numbers, lags)
+
+            def mlp_logits(c0, c1):
+                with torch.no_grad():
+                    return net(torch.from_numpy(X[c0:c1])).numpy()
+
+            res = _evaluate_numpy(mlp_logits, host_masks[lags:], margin, n, loss, edges)
+    rep = res["calibration"]
+    print(f"{n - margin} validation rows, {head['model']} ({loss} head, {head['engine']})")
+    print(CAL.format_report(rep, edges))
+    return {**head, "loss": loss, "rows": n - margin, "val": res["val"], "calibration": rep, "edges": list(edges)}
