@@ -12,6 +12,8 @@ runs the whole pipeline (``Main.java:35``).  Here:
     euromillioner predict --ckpt model.zip [--data-source csv --data-path draws.csv] [--tickets 5 --temperature 1.0]
     euromillioner backtest --ckpt model.zip --tickets 16   # prize tiers of sampled tickets on the validation split
     euromillioner evaluate --ckpt model.zip|.cnt|.npz|.json   # validation metrics + reliability table, Brier score, ECE
+    euromillioner calibrate --ckpt model.zip|.cnt|.npz|.json [--out F] [--fit-pct 0.5] [--fit-rows r]   # fit a per-group scale (and shift) on held-out rows
+    euromillioner evaluate --ckpt model.zip --calibrator model.zip.cal   # the rows after the fit range, through the calibrator
     euromillioner explain --ckpt model.json [--top 3]      # which of the last draw's numbers push each GBDT pick (TreeSHAP)
     euromillioner explain --ckpt forest.npz [--top 3]      # the same for a forest checkpoint, over its last `lags` draws
     euromillioner gen --n 1000000 --planted 0.9 --out draws.csv
@@ -58,7 +60,8 @@ _FLAGS = {
     "--profile-dir": "log.profile_dir", "--profile-steps": "log.profile_steps",
     "--tickets": "tickets.n", "--temperature": "tickets.temperature", "--ticket-seed": "tickets.seed",
     "--ckpt": "ckpt.path", "--resume": "ckpt.resume", "--ckpt-every": "ckpt.every",
-    "--edges": "eval.edges",
+    "--edges": "eval.edges", "--calibrator": "eval.calibrator", "--fit-pct": "eval.fit_pct",
+    "--fit-rows": "eval.fit_rows", "--out": "eval.out",
     "--log-level": "log.level", "--device": "device",
 }
 
@@ -99,6 +102,9 @@ def build_parser() -> argparse.ArgumentParser:
     _add_common(p)
     p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "counts"])
     p = sub.add_parser("evaluate", help="score any checkpoint on the validation split: draw metrics + calibration report")
+    _add_common(p)
+    p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "rf", "gbdt", "counts"])
+    p = sub.add_parser("calibrate", help="fit a per-group scaling of a checkpoint's logits on held-out rows; writes a .cal file")
     _add_common(p)
     p.add_argument("--model", default=None, choices=["mlp", "mlp-wide", "rf", "gbdt", "counts"])
     p = sub.add_parser("explain", help="TreeSHAP: the features behind each number a GBDT (.json) or forest (.npz) checkpoint picks")
@@ -181,6 +187,10 @@ def main(argv=None) -> int:
             from .train import evaluate
 
             res = evaluate(cfg, model=a.model)
+        elif a.cmd == "calibrate":
+            from .train import calibrate
+
+            res = calibrate(cfg, model=a.model)
         elif a.cmd == "explain":
             from .train import explain_next
 

@@ -157,6 +157,10 @@ class TicketConfig:
 @dataclasses.dataclass
 class EvalConfig:
     edges: str | None = None  # evaluate: comma list of up to 15 ascending probability edges (None: calibration.DEFAULT_EDGES)
+    fit_pct: float = 0.5  # calibrate: the share of the validation samples the scaling is fitted on (the first ones)
+    fit_rows: int = 1 << 22  # calibrate: at most this many fit rows (2^22 rows are 1 GiB of fp32 logits)
+    calibrator: str | None = None  # evaluate: a .cal file; the samples after its fit range are scored through it
+    out: str | None = None  # calibrate: where the .cal file goes (None: <ckpt>.cal)
 
 
 @dataclasses.dataclass

@@ -28,6 +28,7 @@ from __future__ import annotations
 import math
 import os
 import time
+from typing import Any, NamedTuple
 
 import numpy as np
 import torch
@@ -1084,17 +1085,33 @@ def _evaluate_numpy(logits_of, targets: np.ndarray, a: int, b: int, loss: str, e
     return {"val": val, "calibration": CAL.report(totals, b - a, loss, edges)}
 
 
-def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
-    """``euromillioner evaluate``: score a checkpoint of any of the five model kinds on the positional validation
-    split (the kind is read from the checkpoint; ``model``, the CLI's ``--model``, must agree with it when given): the draw metrics of ``train`` plus a calibration report (reliability table per group, Brier score,
-    expected calibration error; :mod:`euromillioner_amd.calibration`).  On a GPU the logits stay on the device
-    (``ops.calibration``); ``--device cpu`` runs the numpy specification on the model's host logits."""
-    from . import calibration as CAL
+class _EvalSetup(NamedTuple):
+    """What scoring a checkpoint needs, whatever its kind (:func:`_eval_setup`).  On a GPU ``logits_of(b, offset,
+    sidx)`` returns device logits [b, >= 64] that are scored against ``targets[idx + 1]`` (device masks), in chunks of
+    ``chunk``; on the host ``logits_of(c0, c1)`` returns the logits of samples [c0, c1), scored against the host
+    masks ``targets[c0:c1]``."""
+    path: str
+    head: dict
+    edges: tuple
+    use_gpu: bool
+    loss: str
+    lags: int
+    margin: int
+    n: int
+    logits_of: Any
+    targets: Any
+    chunk: int
+
+
+def _eval_setup(cfg: RunConfig, model: str | None, what: str) -> _EvalSetup:
+    """The per-kind set-up of ``evaluate`` and ``calibrate``: the checkpoint kind (read from the file; ``model``, the
+    CLI's ``--model``, must agree with it when given), its logits, the target masks, the loss, the validation
+    samples ``[margin, n)`` and the head of the result."""
     from .data.draws import mask_bits
 
     path = cfg.ckpt.resume or cfg.ckpt.path
     if not path:
-        raise ValueError("evaluate needs --ckpt pointing at a checkpoint")
+        raise ValueError(f"{what} needs --ckpt pointing at a checkpoint")
     if not os.path.exists(path):
         raise FileNotFoundError(path)
     kind = {".npz": "rf", ".json": "gbdt", ".cnt": "counts"}.get(os.path.splitext(path)[1], "mlp")
@@ -1105,6 +1122,7 @@ def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
     ds = load_draws(cfg)
     host_masks = mask_bits(ds.numbers).view(np.int64)
     head: dict = {"checkpoint": path, "engine": "hip" if use_gpu else "numpy"}
+    chunk = 1 << 20
 
     def split(lags: int) -> tuple[int, int]:
         n = len(ds) - lags
@@ -1124,29 +1142,25 @@ def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
         rf = RandomForest.load(path)
         lags = int(rf.F) // 62
         if lags < 1 or int(rf.F) != 62 * lags:
-            raise ValueError(f"evaluate needs a next-draw forest over 62 features per draw, this checkpoint has {rf.F}")
+            raise ValueError(f"{what} needs a next-draw forest over 62 features per draw, this checkpoint has {rf.F}")
         margin, n = split(lags)
         loss = "bce"
         head.update(model="rf", lags=lags, trees=int(len(rf.feat)))
         if use_gpu:
-            from .ops import calibration as OC
             from .ops import tree_inputs as TI
 
             masks = device_masks()
-            tgt = masks[lags - 1:] if lags > 1 else masks  # as pipeline.device_draw_metrics
+            targets = masks[lags - 1:] if lags > 1 else masks  # as pipeline.device_draw_metrics
 
             def logits_of(b, o, si):
                 return rf.predict_proba_device(TI.rf_rows(masks, lags, first=o, count=b)[0], out_logit=True)
-
-            res = OC.calibrate_logits(logits_of, tgt, n - margin, loss, edges, offset=margin)
         else:
             X, _ = lag_features(ds.numbers, lags)
+            targets = host_masks[lags:]
 
-            def logits_np_of(c0, c1):
+            def logits_of(c0, c1):
                 p = rf.predict_proba(pack_bits(X[c0:c1]))
                 return torch.logit(torch.from_numpy(p).double().clamp(1e-7, 1 - 1e-7)).float().numpy()  # as train_rf
-
-            res = _evaluate_numpy(logits_np_of, host_masks[lags:], margin, n, loss, edges)
     elif path.endswith(".json"):
         from .data.draws import featurize_raw
         from .models.gbdt import GBDT
@@ -1154,9 +1168,10 @@ def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
 
         g = GBDT.load(path)
         if g.n_tasks != 62 or g.objective not in ("reg:logistic", "binary:logistic"):
-            raise ValueError(f"evaluate needs a 62-booster logistic next-draw GBDT; this checkpoint has {g.n_tasks} "
+            raise ValueError(f"{what} needs a 62-booster logistic next-draw GBDT; this checkpoint has {g.n_tasks} "
                              f"booster(s) with objective {g.objective}")
         nf = num_features(g)
+        lags = 1
         margin, n = split(1)
         loss = "bce"
         head.update(model="gbdt", features=nf)
@@ -1170,9 +1185,7 @@ def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
             return g.predict_margin(x)
 
         if use_gpu:
-            from .ops import calibration as OC
-
-            masks = device_masks()
+            targets = masks = device_masks()
             if nf == 62:
                 def logits_of(b, o, si):
                     return g.predict_margin_draw_masks(masks, (o, o + b))
@@ -1181,25 +1194,27 @@ def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
                     z = torch.zeros(b, 64, dtype=torch.float32)
                     z[:, :62] = torch.from_numpy(np.asarray(host_margin(o, o + b), dtype=np.float32))
                     return z.cuda()
-
-            res = OC.calibrate_logits(logits_of, masks, n - margin, loss, edges, offset=margin)
         else:
-            res = _evaluate_numpy(host_margin, host_masks[1:], margin, n, loss, edges)
+            logits_of, targets = host_margin, host_masks[1:]
     elif path.endswith(".cnt"):
         from .models.count_table import CountTable
 
         ct = CountTable.load(path, "cuda" if use_gpu else "cpu")
+        lags = ct.lags
         margin, n = split(ct.lags)
         loss = "softmax"
         head.update(model="counts", lags=ct.lags)
         if use_gpu:
-            from .ops import calibration as OC
-
             masks = device_masks()
-            res = OC.calibrate_model(ct, masks, n - margin, loss, edges, offset=margin, target_masks=ct._tmasks(masks))
+            targets = ct._tmasks(masks)
+
+            def logits_of(b, o, si):
+                return ct.logits(masks, b, offset=o, sidx=si)
         else:
-            res = _evaluate_numpy(lambda c0, c1: ct.logits_np(host_masks, np.arange(c0, c1)), host_masks[ct.lags:],
-                                  margin, n, loss, edges)
+            targets = host_masks[ct.lags:]
+
+            def logits_of(c0, c1):
+                return ct.logits_np(host_masks, np.arange(c0, c1))
     else:
         from .models.mlp import DrawMLP
 
@@ -1211,32 +1226,151 @@ def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
         head.update(model="mlp", sizes=list(sizes), lags=lags)
         if use_gpu:
             from .models.mlp import FusedSmallMLP
-            from .ops import calibration as OC
 
             masks = device_masks()
+            chunk = 1 << 16
             if sizes == (62, 128, 62) and act == "relu":
-                model = FusedSmallMLP("cuda", loss=loss, dtype=cfg.mlp.dtype,
-                                      state_dict={_FusedEngine._MAP[k]: v for k, v in ck["state_dict"].items()})
-                tgt = None
+                net = FusedSmallMLP("cuda", loss=loss, dtype=cfg.mlp.dtype,
+                                    state_dict={_FusedEngine._MAP[k]: v for k, v in ck["state_dict"].items()})
+                targets = masks
             else:
                 from .models.gemm_mlp import GemmMLPTrainer
 
-                model = GemmMLPTrainer(sizes, "cuda", activation=act, loss=loss, state_dict=ck["state_dict"],
-                                       dtype=cfg.mlp.dtype, lags=lags)
-                tgt = model._tmasks(masks)
-            res = OC.calibrate_model(model, masks, n - margin, loss, edges, offset=margin, chunk=1 << 16,
-                                     target_masks=tgt)
+                net = GemmMLPTrainer(sizes, "cuda", activation=act, loss=loss, state_dict=ck["state_dict"],
+                                     dtype=cfg.mlp.dtype, lags=lags)
+                targets = net._tmasks(masks)
+
+            def logits_of(b, o, si):
+                return net.logits(masks, b, offset=o, sidx=si)
         else:
             net = DrawMLP(sizes, activation=act, loss=loss, use_hip=False)
             net.load_state_dict(ck["state_dict"])
             X, _ = lag_features(ds.numbers, lags)
+            targets = host_masks[lags:]
 
-            def mlp_logits(c0, c1):
+            def logits_of(c0, c1):
                 with torch.no_grad():
                     return net(torch.from_numpy(X[c0:c1])).numpy()
+    return _EvalSetup(path, head, edges, use_gpu, loss, int(lags), margin, n, logits_of, targets, chunk)
 
-            res = _evaluate_numpy(mlp_logits, host_masks[lags:], margin, n, loss, edges)
+
+def _score(s: _EvalSetup, first: int, cal=None) -> dict:
+    """``{"val", "calibration"}`` of the samples ``[first, n)`` of a set-up, through the calibrator ``cal`` if given."""
+    if s.use_gpu:
+        from .ops import calibration as OC
+
+        logits_of = s.logits_of
+        if cal is not None:
+            from .ops import calibration_fit as CF
+
+            def logits_of(b, o, si):
+                return CF.apply_scaling(s.logits_of(b, o, si), b, cal.a, cal.b)
+
+        return OC.calibrate_logits(logits_of, s.targets, s.n - first, s.loss, s.edges, offset=first, chunk=s.chunk)
+    logits_of = s.logits_of if cal is None else (lambda c0, c1: cal.apply_np(s.logits_of(c0, c1)))
+    return _evaluate_numpy(logits_of, s.targets, first, s.n, s.loss, s.edges)
+
+
+def _check_calibrator(cal, s: _EvalSetup, path: str) -> None:
+    """A calibrator is for one checkpoint kind, head and lag count, and must leave samples to score."""
+    rec = cal.record
+    if rec.get("model") != s.head["model"] or cal.loss != s.loss or rec.get("lags") != s.lags:
+        raise ValueError(f"{os.path.basename(path)} was fitted for a {rec.get('model')} checkpoint ({cal.loss} head, "
+                         f"lags {rec.get('lags')}); this one is {s.head['model']} ({s.loss} head, lags {s.lags})")
+    last = rec.get("last")
+    if not isinstance(last, int) or not s.margin <= last < s.n:
+        raise ValueError(f"{os.path.basename(path)} was fitted on samples up to {last}: no validation sample of "
+                         f"[{s.margin}, {s.n}) is left to score")
+
+
+def evaluate(cfg: RunConfig, model: str | None = None) -> dict:
+    """``euromillioner evaluate``: score a checkpoint of any of the five model kinds on the positional validation
+    split (the kind is read from the checkpoint; ``model``, the CLI's ``--model``, must agree with it when given): the draw metrics of ``train`` plus a calibration report (reliability table per group, Brier score,
+    expected calibration error; :mod:`euromillioner_amd.calibration`).  On a GPU the logits stay on the device
+    (``ops.calibration``); ``--device cpu`` runs the numpy specification on the model's host logits.
+
+    With ``eval.calibrator`` (``--calibrator F``, a ``.cal`` file of ``calibrate``) the samples after the calibrator's
+    fit range, ``[cal.last, n)``, are scored through it."""
+    from . import calibration as CAL
+
+    s = _eval_setup(cfg, model, "evaluate")
+    cal, first, note, extra = None, s.margin, "", {}
+    if cfg.eval.calibrator is not None:
+        from .scaling import Calibrator
+
+        cpath = str(cfg.eval.calibrator)
+        if not os.path.exists(cpath):
+            raise FileNotFoundError(cpath)
+        cal = Calibrator.load(cpath)
+        _check_calibrator(cal, s, cpath)
+        first = int(cal.record["last"])
+        note = f", samples [{first}, {s.n}) through {os.path.basename(cpath)}"
+        extra = {"first": first, "calibrator": cal.to_dict()}
+    res = _score(s, first, cal)
     rep = res["calibration"]
-    print(f"{n - margin} validation rows, {head['model']} ({loss} head, {head['engine']})")
-    print(CAL.format_report(rep, edges))
-    return {**head, "loss": loss, "rows": n - margin, "val": res["val"], "calibration": rep, "edges": list(edges)}
+    print(f"{s.n - first} validation rows, {s.head['model']} ({s.loss} head, {s.head['engine']}){note}")
+    print(CAL.format_report(rep, s.edges))
+    return {**s.head, "loss": s.loss, "rows": s.n - first, "val": res["val"], "calibration": rep,
+            "edges": list(s.edges), **extra}
+
+
+# ---------------------------------------------------------------------------------------------
+# calibrate: fit a per-group scaling of a checkpoint's logits on held-out rows
+# ---------------------------------------------------------------------------------------------
+def calibrate(cfg: RunConfig, model: str | None = None) -> dict:
+    """``euromillioner calibrate``: fit the per-group scale (and, under the sigmoid head, shift) of a checkpoint's
+    logits (:mod:`euromillioner_amd.scaling`) on the first ``floor(eval.fit_pct (n - margin))`` validation samples,
+    at most ``eval.fit_rows`` of them, score the remaining ones raw and calibrated, and write the ``.cal`` file to
+    ``eval.out`` (default ``<ckpt>.cal``).  On a GPU the fit rows' logits fill one device buffer and every Newton
+    pass is one kernel launch over it (``ops.calibration_fit``); ``--device cpu`` runs the numpy specification.
+    Single process.  Returns ``{"before", "after"`` (each the ``val`` and ``calibration`` of ``evaluate``),
+    ``"calibrator"}`` next to the head of ``evaluate``."""
+    from . import calibration as CAL
+    from . import scaling as SC
+
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("calibrate runs in a single process (no --dp, no torchrun)")
+    fit_pct, fit_rows = float(cfg.eval.fit_pct), int(cfg.eval.fit_rows)
+    if not 0.0 < fit_pct < 1.0:
+        raise ValueError(f"eval.fit_pct={cfg.eval.fit_pct!r}: a share inside (0, 1)")
+    if fit_rows < 1:
+        raise ValueError(f"eval.fit_rows={cfg.eval.fit_rows!r}: at least 1")
+    s = _eval_setup(cfg, model, "calibrate")
+    rows = min(int(math.floor(fit_pct * (s.n - s.margin))), fit_rows)
+    last = s.margin + rows
+    if rows < 1 or last >= s.n:
+        raise ValueError(f"{s.n - s.margin} validation samples at fit_pct {fit_pct} leave the fit or the scoring "
+                         "without rows")
+    if s.use_gpu:
+        from .ops import calibration_fit as CF
+
+        buf, done = torch.empty(rows, 64, dtype=torch.float32, device="cuda"), 0
+        while done < rows:
+            b = min(s.chunk, rows - done)
+            buf[done:done + b] = s.logits_of(b, s.margin + done, None)[:, :64]
+            done += b
+        fit = CF.fit_device(buf, s.targets, rows, s.loss, offset=s.margin)
+        del buf
+    else:
+        z = np.concatenate([np.asarray(s.logits_of(c0, min(last, c0 + (1 << 14))), dtype=np.float32)[:, :62]
+                            for c0 in range(s.margin, last, 1 << 14)])
+        fit = SC.fit_np(z, s.targets[s.margin:last], s.loss)
+    cal = SC.Calibrator(s.loss, fit["a"], fit["b"], {
+        "model": s.head["model"], "lags": s.lags, "first": s.margin, "last": last, "rows": rows,
+        "iterations": [int(v) for v in fit["iterations"]], "converged": [bool(v) for v in fit["converged"]],
+        "loss_before": SC.row_loss(fit["L_before"][:, None], rows, s.loss),
+        "loss_after": SC.row_loss(fit["L_after"][:, None], rows, s.loss), "checkpoint": os.path.basename(s.path)})
+    before, after = _score(s, last), _score(s, last, cal)
+    out = str(cfg.eval.out) if cfg.eval.out is not None else s.path + ".cal"
+    cal.save(out)
+    print(f"fitted on samples [{s.margin}, {last}), scored on [{last}, {s.n}): {s.head['model']} ({s.loss} head, "
+          f"{s.head['engine']})")
+    for g, name in enumerate(CAL.GROUPS):
+        print(f"{name}: a {float(cal.a[g]):.6g}  b {float(cal.b[g]):.6g}  ({fit['iterations'][g]} iterations, "
+              f"{'converged' if fit['converged'][g] else 'stopped'})")
+        for tag, r in (("before", before), ("after", after)):
+            c = r["calibration"][name]
+            print(f"  {tag:<7} ece {c['ece']:.6f}  brier/row {c['brier']:.6f}  loss {r['val']['loss']:.6f}")
+    print(f"loss per fit row {cal.record['loss_before']:.6f} -> {cal.record['loss_after']:.6f}; wrote {out}")
+    return {**s.head, "loss": s.loss, "rows": s.n - last, "fit_rows": rows, "before": before, "after": after,
+            "calibrator": cal.to_dict(), "out": out, "edges": list(s.edges)}
